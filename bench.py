@@ -9,13 +9,19 @@ reference's CPU-runnable case; configs 3-5 are covered by SCALE runs and the
 parity/verify tests).
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+                        [--dump-outputs DIR] [--full]
 N>1 is launched by the driver via torch.distributed.run, one rank per GPU
 over RCCL; ranks shard the label index space (weak scaling: per-GPU labels
 fixed) and the only exchange is the final VRF-nonce min-reduce.
 
-Rank 0 prints ONE JSON line: whole-job labels/s over all ranks, kernel-level
-roofline of the dominant kernel (HIP events on the engine stream), and the
-CPU-oracle baseline timed on this box's host cores.
+Rank 0 prints ONE JSON line: whole-job labels/s over all ranks and the
+kernel-level roofline of the dominant kernel (HIP events on the engine
+stream, taken during the timed steps themselves).  A plain run does nothing
+else; --full adds the CPU-oracle baseline timed on this box's host cores.
+
+--dump-outputs DIR writes, after the timed steps, what the init path
+produced in its last timed step as DIR/<name>.npy (see dump_outputs).  The
+inputs are fixed constants, so two builds can be compared file for file.
 """
 import argparse
 import json
@@ -70,12 +76,72 @@ def cpu_baseline():
                 "kind": "port", "sample": f"failed: {e}"}
 
 
+DUMP_SAMPLE_LABELS = 1 << 18   # labels sampled from the last step (16 MB)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, gsm_amd, device_id, step_start, nonce):
+    """Write what the init path produced in its last timed step.
+
+    The benched configuration streams its labels to the in-memory sink,
+    which drops them (256 GiB of label space does not stay resident), so the
+    caller of mgr.step() receives only the label count and the running VRF
+    nonce.  The labels of the last timed step's index range
+    [step_start, step_start + STEP_LABELS) are therefore produced once more
+    by a second session of the same engine entry point (post_init_step, same
+    identity, scryptN and batch geometry) restricted to that range, which is
+    small enough for the engine to keep on the device and hand back.
+
+    Files (float32 unless noted; every value is an exact small integer):
+      labels.npy        (DUMP_SAMPLE_LABELS, 16) label bytes, a fixed seeded
+                        sample of the step's labels in ascending index order
+      label_index.npy   (DUMP_SAMPLE_LABELS,) float64 global label indices
+      vrf_nonce_index.npy  (1,) float64, the timed session's running minimum
+      vrf_nonce_label.npy  (32,) its label bytes (both empty if none found)
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total_labels = NUM_UNITS * LABELS_PER_UNIT
+    opts = gsm_amd.PostSetupOpts(
+        num_units=NUM_UNITS, scrypt_n=SCRYPT_N, provider_id=device_id,
+        index_start=step_start, index_end=step_start + STEP_LABELS,
+        data_dir=None,
+        scratch_bytes=int(os.environ.get("POST_BENCH_SCRATCH", "0")))
+    assert opts.index_end <= total_labels
+    mgr = gsm_amd.PostSetupManager(bytes([0xA5]) * 32, bytes([0x5A]) * 32,
+                                   gsm_amd.PostConfig(), opts)
+    mgr.prepare_initializer()
+    done, _ = mgr.step(STEP_LABELS)
+    assert done == STEP_LABELS
+    raw = np.frombuffer(mgr.copy_labels(0, STEP_LABELS), dtype=np.uint8)
+    mgr.reset()
+    raw = raw.reshape(STEP_LABELS, gsm_amd.api.LABEL_SIZE)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(
+        STEP_LABELS, size=DUMP_SAMPLE_LABELS, replace=False))
+    np.save(os.path.join(out_dir, "labels.npy"),
+            raw[pick].astype(np.float32))
+    np.save(os.path.join(out_dir, "label_index.npy"),
+            (pick + step_start).astype(np.float64))
+    np.save(os.path.join(out_dir, "vrf_nonce_index.npy"),
+            np.array([nonce[0]] if nonce else [], dtype=np.float64))
+    np.save(os.path.join(out_dir, "vrf_nonce_label.npy"),
+            np.frombuffer(nonce[1] if nonce else b"",
+                          dtype=np.uint8).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU-oracle baseline (a plain run "
+                         "measures the headline figure only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     if not torch.cuda.is_available():
@@ -209,13 +275,20 @@ def main():
                 "vrf_nonce_found": bool(global_nonce),
             },
             "roofline": roofline,
-            "cpu_baseline": cpu_baseline(),
+            "cpu_baseline": cpu_baseline() if args.full else {
+                "value": None, "unit": "labels/s", "cores": 0,
+                "kind": "port", "sample": "skipped (plain run; see --full)"},
             "hbm_write_fraction_16B": round(
                 value / world * 16 / (HBM_PEAK_GBS * 1e9), 6),
         }
-        print(json.dumps(result))
 
     mgr.reset()
+    if rank == 0:
+        if args.dump_outputs:
+            last_step = start + (args.warmup + args.steps - 1) * STEP_LABELS
+            dump_outputs(args.dump_outputs, gsm_amd, device_id, last_step,
+                         local_nonce)
+        print(json.dumps(result))
     if dist:
         dist.destroy_process_group()
 

@@ -11,7 +11,7 @@ echo "== 1. full GPU suite"
 timeout -k 10 600 python -m pytest tests -m gpu -q 2>&1 | tail -3
 
 echo "== 2. headline bench (driver contract, default flags)"
-timeout -k 10 600 python bench.py --steps 8 --warmup 2 \
+timeout -k 10 600 python bench.py --full --steps 8 --warmup 2 \
   2> "$OUT/r2_bench.err" | tee "$OUT/r2_bench.json"
 
 echo "== 3. rocprof kernel stats over a short bench (cross-check)"
