@@ -68,6 +68,9 @@ hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
 hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
                                     uint32_t blocks, hipStream_t stream);
 uint64_t poste_label_resident_slots(uint32_t gap_shift);
+/* host-only: does the launcher run the lean gap-1 ROMix kernel here? */
+int poste_label_romix_lean_ok(uint32_t scrypt_n, uint32_t gap_shift,
+                              uint64_t scratch_lanes);
 }
 
 #endif

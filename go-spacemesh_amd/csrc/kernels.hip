@@ -133,10 +133,10 @@ __device__ __forceinline__ void salsa8_z(uint32_t &A, uint32_t &B,
     a ^= __builtin_rotateleft32(d + c, 18);
     /* row round: QR(z0, rot1(z3), rot2(z2), rot3(z1)).  The compiler
      * fuses these permutes into the consuming xor/add as *_dpp forms; the
-     * VALU->DPP hazard s_nops that remain are issue-equivalent to unfused
-     * movs (measured: source order and dual-stream interleave both
-     * neutral — the kernel sits at the mixed read+write HBM ceiling,
-     * profiles/r01_kernel_profile.md). */
+     * VALU->DPP hazard s_nops that remain cost nothing at 8 waves/SIMD:
+     * other waves issue into them (measured: source order neutral,
+     * two interleaved labels per quad slower — profiles/r03_romix_isa.md,
+     * profiles/r03_kernel_stats.md). */
     uint32_t y1 = SWZ(d, QROT1);
     uint32_t y2 = SWZ(c, QROT2);
     uint32_t y3 = SWZ(b, QROT3);
@@ -150,64 +150,6 @@ __device__ __forceinline__ void salsa8_z(uint32_t &A, uint32_t &B,
     b = SWZ(y3, QROT1);
   }
   A += a; B += b; C += c; D += d;
-}
-
-/* dual-stream salsa20/8: two independent quads' states interleaved so the
- * in-order wave always has a second dependency chain to issue from */
-__device__ __forceinline__ void salsa8_z2(uint32_t &A0, uint32_t &B0,
-                                          uint32_t &C0, uint32_t &D0,
-                                          uint32_t &A1, uint32_t &B1,
-                                          uint32_t &C1, uint32_t &D1) {
-  uint32_t a0 = A0, b0 = B0, c0 = C0, d0 = D0;
-  uint32_t a1 = A1, b1 = B1, c1 = C1, d1 = D1;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    b0 ^= __builtin_rotateleft32(a0 + d0, 7);
-    b1 ^= __builtin_rotateleft32(a1 + d1, 7);
-    c0 ^= __builtin_rotateleft32(b0 + a0, 9);
-    c1 ^= __builtin_rotateleft32(b1 + a1, 9);
-    d0 ^= __builtin_rotateleft32(c0 + b0, 13);
-    d1 ^= __builtin_rotateleft32(c1 + b1, 13);
-    a0 ^= __builtin_rotateleft32(d0 + c0, 18);
-    a1 ^= __builtin_rotateleft32(d1 + c1, 18);
-    uint32_t y30 = SWZ(b0, QROT3), y31 = SWZ(b1, QROT3);
-    uint32_t y20 = SWZ(c0, QROT2), y21 = SWZ(c1, QROT2);
-    uint32_t y10 = SWZ(d0, QROT1), y11 = SWZ(d1, QROT1);
-    y10 ^= __builtin_rotateleft32(a0 + y30, 7);
-    y11 ^= __builtin_rotateleft32(a1 + y31, 7);
-    y20 ^= __builtin_rotateleft32(y10 + a0, 9);
-    y21 ^= __builtin_rotateleft32(y11 + a1, 9);
-    y30 ^= __builtin_rotateleft32(y20 + y10, 13);
-    y31 ^= __builtin_rotateleft32(y21 + y11, 13);
-    a0 ^= __builtin_rotateleft32(y30 + y20, 18);
-    a1 ^= __builtin_rotateleft32(y31 + y21, 18);
-    d0 = SWZ(y10, QROT3);
-    d1 = SWZ(y11, QROT3);
-    c0 = SWZ(y20, QROT2);
-    c1 = SWZ(y21, QROT2);
-    b0 = SWZ(y30, QROT1);
-    b1 = SWZ(y31, QROT1);
-  }
-  A0 += a0; B0 += b0; C0 += c0; D0 += d0;
-  A1 += a1; B1 += b1; C1 += c1; D1 += d1;
-}
-
-/* dual-stream BlockMix r=1 */
-__device__ __forceinline__ void blockmix2_z(uint32_t XA0[4], uint32_t XA1[4],
-                                            uint32_t XB0[4],
-                                            uint32_t XB1[4]) {
-  uint32_t ta0 = XA0[0] ^ XA1[0], ta1 = XA0[1] ^ XA1[1],
-           ta2 = XA0[2] ^ XA1[2], ta3 = XA0[3] ^ XA1[3];
-  uint32_t tb0 = XB0[0] ^ XB1[0], tb1 = XB0[1] ^ XB1[1],
-           tb2 = XB0[2] ^ XB1[2], tb3 = XB0[3] ^ XB1[3];
-  salsa8_z2(ta0, ta1, ta2, ta3, tb0, tb1, tb2, tb3);
-  XA0[0] = ta0; XA0[1] = ta1; XA0[2] = ta2; XA0[3] = ta3;
-  XB0[0] = tb0; XB0[1] = tb1; XB0[2] = tb2; XB0[3] = tb3;
-  ta0 ^= XA1[0]; ta1 ^= XA1[1]; ta2 ^= XA1[2]; ta3 ^= XA1[3];
-  tb0 ^= XB1[0]; tb1 ^= XB1[1]; tb2 ^= XB1[2]; tb3 ^= XB1[3];
-  salsa8_z2(ta0, ta1, ta2, ta3, tb0, tb1, tb2, tb3);
-  XA1[0] = ta0; XA1[1] = ta1; XA1[2] = ta2; XA1[3] = ta3;
-  XB1[0] = tb0; XB1[1] = tb1; XB1[2] = tb2; XB1[3] = tb3;
 }
 
 /* BlockMix r=1 on a quad: X = (B0,B1) as two z-vectors per lane (8 regs) */
@@ -347,9 +289,10 @@ post_label_prologue_kernel(LabelKernelArgs a) {
   }
 }
 
-/* the ROMix hot loop: register-lean, forced to 8 waves/SIMD */
+/* generic ROMix: any lookup-gap (POST_GAP_SHIFT > 0), and gap 1 when the
+ * scratch geometry is outside what the lean kernel below addresses */
 __global__ void __launch_bounds__(POSTE_THREADS, 8)
-post_label_romix_kernel(LabelKernelArgs a) {
+post_label_romix_gap_kernel(LabelKernelArgs a) {
   const unsigned long long lane =
       (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long group = lane >> 2;
@@ -416,83 +359,90 @@ post_label_romix_kernel(LabelKernelArgs a) {
   }
 }
 
-/* dual-stream ROMix (lookup-gap 1 only): each quad advances TWO labels so
- * the in-order wave interleaves two independent salsa chains — the
- * SQ_WAIT_INST_ANY issue-stall fix (profiles/pmc_sq: 54% of wave cycles).
- * In-flight slots = 2 x grid quads (= a.scratch_lanes). */
+/* ---- lean lookup-gap-1 ROMix ----
+ * VALU issue is the busiest resource of this kernel
+ * (profiles/r03_romix_isa.md), so vector instructions around the two salsa
+ * calls of an iteration cost throughput.  The gap-1 kernel carries no gap
+ * machinery and addresses the scratch with 24-bit multiplies: stored block
+ * j of a quad lies j * (scratch_lanes * 8) uint4 past the quad's own base
+ * pointer.  The launcher only picks it when scrypt_n <= 2^24 and
+ * scratch_lanes * 8 < 2^24, so both factors fit v_mul_u32_u24 /
+ * v_mul_hi_u32_u24 (full rate) and one v_lshl_add_u64 forms the address —
+ * no 64-bit multiply or shift.  The `& 0xffffff` below never changes a
+ * value; it tells the compiler the range. */
+#define POSTE_U24 0xffffffu
+
+__device__ __forceinline__ const uint4 *vblock(const uint4 *qbase, uint32_t j,
+                                               uint32_t stride16) {
+  return qbase + (unsigned long long)j * stride16;
+}
+
+/* a ^ b ^ c as one v_bitop3_b32 (truth table 0x96).  Written `a ^ b ^ c`
+ * the compiler reassociates it back into two 2-input xors. */
+#define XOR3(a, b, c) ((uint32_t)__builtin_amdgcn_bitop3_b32((a), (b), (c), 0x96))
+
+/* phase-2 step: X ^= V; X = BlockMix(X).  X0 ^ V0 is needed only as part
+ * of the first salsa input X0 ^ V0 ^ (X1 ^ V1), a 3-input xor: 8 xors per
+ * lane instead of 12. */
+__device__ __forceinline__ void blockmix_xor_z(uint32_t X0[4], uint32_t X1[4],
+                                               const uint4 v0,
+                                               const uint4 v1) {
+  X1[0] ^= v1.x; X1[1] ^= v1.y; X1[2] ^= v1.z; X1[3] ^= v1.w;
+  uint32_t t0 = XOR3(X0[0], v0.x, X1[0]), t1 = XOR3(X0[1], v0.y, X1[1]),
+           t2 = XOR3(X0[2], v0.z, X1[2]), t3 = XOR3(X0[3], v0.w, X1[3]);
+  salsa8_z(t0, t1, t2, t3);
+  X0[0] = t0; X0[1] = t1; X0[2] = t2; X0[3] = t3;
+  t0 ^= X1[0]; t1 ^= X1[1]; t2 ^= X1[2]; t3 ^= X1[3];
+  salsa8_z(t0, t1, t2, t3);
+  X1[0] = t0; X1[1] = t1; X1[2] = t2; X1[3] = t3;
+}
+
+/* the ROMix hot loop at lookup-gap 1: register-lean, 8 waves/SIMD */
 __global__ void __launch_bounds__(POSTE_THREADS, 8)
-post_label_romix2_kernel(LabelKernelArgs a) {
+post_label_romix_kernel(LabelKernelArgs a) {
   const unsigned long long lane =
       (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long group = lane >> 2;
   const uint32_t sub = (uint32_t)(lane & 3);
-  const unsigned long long gquads =
-      ((unsigned long long)gridDim.x * blockDim.x) >> 2;
   const uint32_t n = a.scrypt_n;
-  const uint32_t mask = n - 1;
-  uint4 *V = (uint4 *)a.scratch;
+  const uint32_t mask = (n - 1) & POSTE_U24;
+  const uint32_t stride16 = ((uint32_t)a.scratch_lanes * 8u) & POSTE_U24;
+  /* this quad's column of V: lane sub covers chunks sub and sub+4 of each
+   * 8-uint4 block -> aligned 64-B transactions */
+  uint4 *const qbase = (uint4 *)a.scratch + (group * 8ull + sub);
   uint4 *X = (uint4 *)a.xbuf;
-  const unsigned long long slotA = group * 2, slotB = group * 2 + 1;
 
-  for (unsigned long long base = group * 2; base < a.count;
-       base += 2 * gquads) {
-    const unsigned long long taskA = base;
-    const unsigned long long taskB = base + 1;
-    const bool validB = taskB < a.count;
-    const unsigned long long tb = validB ? taskB : taskA;
-    uint32_t ZA0[4], ZA1[4], ZB0[4], ZB1[4];
+  for (unsigned long long task = group; task < a.count;
+       task += a.scratch_lanes) {
+    uint32_t Z0[4], Z1[4];
     {
-      uint4 *pA = X + taskA * 8ull;
-      uint4 *pB = X + tb * 8ull;
-      uint4 a0 = pA[sub], a1 = pA[sub + 4];
-      uint4 b0 = pB[sub], b1 = pB[sub + 4];
-      ZA0[0] = a0.x; ZA0[1] = a0.y; ZA0[2] = a0.z; ZA0[3] = a0.w;
-      ZA1[0] = a1.x; ZA1[1] = a1.y; ZA1[2] = a1.z; ZA1[3] = a1.w;
-      ZB0[0] = b0.x; ZB0[1] = b0.y; ZB0[2] = b0.z; ZB0[3] = b0.w;
-      ZB1[0] = b1.x; ZB1[1] = b1.y; ZB1[2] = b1.z; ZB1[3] = b1.w;
+      uint4 *p = X + task * 8ull;
+      uint4 v0 = p[sub], v1 = p[sub + 4];
+      Z0[0] = v0.x; Z0[1] = v0.y; Z0[2] = v0.z; Z0[3] = v0.w;
+      Z1[0] = v1.x; Z1[1] = v1.y; Z1[2] = v1.z; Z1[3] = v1.w;
     }
-    /* phase 1 */
+    /* phase 1: V_j = X; X = BlockMix(X) */
     {
-      unsigned long long baseA = slotA * 8ull + sub;
-      unsigned long long baseB = slotB * 8ull + sub;
-      const unsigned long long stride = a.scratch_lanes * 8ull;
+      uint4 *p = qbase;
       for (uint32_t j = 0; j < n; j++) {
-        uint4 *pA = V + baseA;
-        uint4 *pB = V + baseB;
-        pA[0] = make_uint4(ZA0[0], ZA0[1], ZA0[2], ZA0[3]);
-        pA[4] = make_uint4(ZA1[0], ZA1[1], ZA1[2], ZA1[3]);
-        pB[0] = make_uint4(ZB0[0], ZB0[1], ZB0[2], ZB0[3]);
-        pB[4] = make_uint4(ZB1[0], ZB1[1], ZB1[2], ZB1[3]);
-        blockmix2_z(ZA0, ZA1, ZB0, ZB1);
-        baseA += stride;
-        baseB += stride;
+        VSTORE(p, make_uint4(Z0[0], Z0[1], Z0[2], Z0[3]));
+        VSTORE(p + 4, make_uint4(Z1[0], Z1[1], Z1[2], Z1[3]));
+        p += stride16;
+        blockmix_z(Z0, Z1);
       }
     }
-    /* phase 2 */
+    /* phase 2: j = Integerify(X) & (n-1); X ^= V_j; BlockMix.  Integerify
+     * = canonical word 16 = B1's z0[0] -> quad broadcast. */
     for (uint32_t i = 0; i < n; i++) {
-      uint32_t jA = SWZ(ZA1[0], QBCAST0) & mask;
-      uint32_t jB = SWZ(ZB1[0], QBCAST0) & mask;
-      const uint4 *pA =
-          V + ((unsigned long long)jA * a.scratch_lanes + slotA) * 8ull + sub;
-      const uint4 *pB =
-          V + ((unsigned long long)jB * a.scratch_lanes + slotB) * 8ull + sub;
-      uint4 va0 = pA[0], va1 = pA[4];
-      uint4 vb0 = pB[0], vb1 = pB[4];
-      ZA0[0] ^= va0.x; ZA0[1] ^= va0.y; ZA0[2] ^= va0.z; ZA0[3] ^= va0.w;
-      ZA1[0] ^= va1.x; ZA1[1] ^= va1.y; ZA1[2] ^= va1.z; ZA1[3] ^= va1.w;
-      ZB0[0] ^= vb0.x; ZB0[1] ^= vb0.y; ZB0[2] ^= vb0.z; ZB0[3] ^= vb0.w;
-      ZB1[0] ^= vb1.x; ZB1[1] ^= vb1.y; ZB1[2] ^= vb1.z; ZB1[3] ^= vb1.w;
-      blockmix2_z(ZA0, ZA1, ZB0, ZB1);
+      const uint32_t j = SWZ(Z1[0], QBCAST0) & mask;
+      const uint4 *p = vblock(qbase, j, stride16);
+      const uint4 v0 = VLOAD(p), v1 = VLOAD(p + 4);
+      blockmix_xor_z(Z0, Z1, v0, v1);
     }
     {
-      uint4 *pA = X + taskA * 8ull;
-      pA[sub] = make_uint4(ZA0[0], ZA0[1], ZA0[2], ZA0[3]);
-      pA[sub + 4] = make_uint4(ZA1[0], ZA1[1], ZA1[2], ZA1[3]);
-      if (validB) {
-        uint4 *pB = X + taskB * 8ull;
-        pB[sub] = make_uint4(ZB0[0], ZB0[1], ZB0[2], ZB0[3]);
-        pB[sub + 4] = make_uint4(ZB1[0], ZB1[1], ZB1[2], ZB1[3]);
-      }
+      uint4 *p = X + task * 8ull;
+      p[sub] = make_uint4(Z0[0], Z0[1], Z0[2], Z0[3]);
+      p[sub + 4] = make_uint4(Z1[0], Z1[1], Z1[2], Z1[3]);
     }
   }
 }
@@ -1136,34 +1086,42 @@ post_verify_pred_kernel(VerifyPredArgs a) {
 /* host-visible launchers (called from engine.cpp) */
 extern "C" {
 
+/* Whether the lean gap-1 ROMix kernel can address this scratch geometry:
+ * its block offset is a 24-bit x 24-bit multiply of j < scrypt_n by the
+ * slot stride scratch_lanes * 8 (in uint4), so scratch_lanes must stay
+ * below 2^21 and scrypt_n within 2^24; the block index
+ * scrypt_n * scratch_lanes is kept inside 32 bits as well.  Both always
+ * hold on a 288 GB part: scratch_lanes never exceeds the resident quads
+ * (256 CUs x 2048 threads / 4 = 2^17, twice that in slots), and the
+ * scratch, 128 B * scrypt_n * scratch_lanes, would pass 512 GiB before the
+ * block index passed 2^32.  Anything else runs the generic kernel. */
+int poste_label_romix_lean_ok(uint32_t scrypt_n, uint32_t gap_shift,
+                              uint64_t scratch_lanes) {
+  return gap_shift == 0 && scrypt_n <= (1u << 24) &&
+         scratch_lanes < (1ull << 21) &&
+         (uint64_t)scrypt_n * scratch_lanes < (1ull << 32);
+}
+
 hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
                                      uint32_t blocks, hipStream_t stream) {
-  /* Dual-stream ROMix (two slots per quad, half the grid) measured
-   * neutral-to-slightly-slower than single-stream at 8 waves/SIMD
-   * (gpurun summary6); kept behind POST_ROMIX2=1 for re-evaluation. */
-  static const bool use2 = [] {
-    const char *e = getenv("POST_ROMIX2");
-    return e && e[0] == '1';
-  }();
-  const bool dual = use2 && args->gap_shift == 0;
-  uint32_t gblocks = dual ? (blocks + 1) / 2 : blocks;
-  hipLaunchKernelGGL(post_label_prologue_kernel, dim3(gblocks),
+  /* Two labels per quad (a dual-stream form of the lean kernel, spill-free
+   * at 58 VGPRs) measured 4% slower than one label per quad and was
+   * removed: profiles/r03_kernel_stats.md. */
+  hipLaunchKernelGGL(post_label_prologue_kernel, dim3(blocks),
                      dim3(POSTE_THREADS), 0, stream, *args);
-  if (dual) {
-    hipLaunchKernelGGL(post_label_romix2_kernel, dim3(gblocks),
-                       dim3(POSTE_THREADS), 0, stream, *args);
-  } else {
+  if (poste_label_romix_lean_ok(args->scrypt_n, args->gap_shift,
+                                args->scratch_lanes)) {
     hipLaunchKernelGGL(post_label_romix_kernel, dim3(blocks),
                        dim3(POSTE_THREADS), 0, stream, *args);
+  } else {
+    hipLaunchKernelGGL(post_label_romix_gap_kernel, dim3(blocks),
+                       dim3(POSTE_THREADS), 0, stream, *args);
   }
-  hipLaunchKernelGGL(post_label_tail_kernel, dim3(gblocks),
+  hipLaunchKernelGGL(post_label_tail_kernel, dim3(blocks),
                      dim3(POSTE_THREADS), 0, stream, *args);
   return hipGetLastError();
 }
 
-/* Max simultaneously-resident label SLOTS (in-flight labels) of the ROMix
- * kernel for the given gap config.  Scratch beyond this is wasted memory:
- * extra workgroups just queue. */
 hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
                                            uint32_t blocks,
                                            hipStream_t stream) {
@@ -1173,11 +1131,14 @@ hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
   return hipGetLastError();
 }
 
+/* Max simultaneously-resident label SLOTS (in-flight labels) of the ROMix
+ * kernel for the given gap config.  Scratch beyond this is wasted memory:
+ * extra workgroups just queue. */
 uint64_t poste_label_resident_slots(uint32_t gap_shift) {
   const void *kern =
       gap_shift == 0
-          ? reinterpret_cast<const void *>(post_label_romix2_kernel)
-          : reinterpret_cast<const void *>(post_label_romix_kernel);
+          ? reinterpret_cast<const void *>(post_label_romix_kernel)
+          : reinterpret_cast<const void *>(post_label_romix_gap_kernel);
   int blocks_per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kern,
                                                    POSTE_THREADS, 0) !=
@@ -1190,10 +1151,7 @@ uint64_t poste_label_resident_slots(uint32_t gap_shift) {
   int cus = 256;
   if (hipGetDeviceProperties(&prop, dev) == hipSuccess)
     cus = prop.multiProcessorCount;
-  uint64_t quads = (uint64_t)blocks_per_cu * cus * (POSTE_THREADS / 4);
-  const char *e = getenv("POST_ROMIX2");
-  const bool dual = e && e[0] == '1' && gap_shift == 0;
-  return dual ? quads * 2 : quads;
+  return (uint64_t)blocks_per_cu * cus * (POSTE_THREADS / 4);
 }
 
 hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
