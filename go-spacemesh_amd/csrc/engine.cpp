@@ -95,6 +95,19 @@ uint32_t pick_gap_shift(uint32_t scrypt_n) {
   return 0;
 }
 
+/* Labels per chunk of the proving scan: 2^24 (256 MiB).
+ * POST_PROVE_CHUNK_LABELS lowers it (floor 256; unset, zero, unparsable or
+ * not lower = 2^24), so a small buffer crosses several chunk boundaries and
+ * reuses both pipeline buffers.  Read per call, as POST_SCAN_MODE is. */
+uint64_t prove_chunk_labels() {
+  const uint64_t dflt = 1ull << 24;
+  const char *env = getenv("POST_PROVE_CHUNK_LABELS");
+  if (!env) return dflt;
+  const long long v = strtoll(env, nullptr, 10);
+  if (v <= 0 || (uint64_t)v >= dflt) return dflt;
+  return v < 256 ? 256 : (uint64_t)v;
+}
+
 /* Cached per-device verification workspace: the worker-pool call pattern
  * (one proof per post_verify call, post_verifier.go:150-160) would
  * otherwise pay scratch/staging allocation on every call.  Calls remain
@@ -976,7 +989,7 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
    * whole label set in host memory).  Expected total hits = nonces*k1
    * (a few thousand) regardless of label count, so hits accumulate in one
    * device buffer drained once at the end. */
-  const uint64_t CHUNK = 1ull << 24; /* 16M labels = 256 MiB per chunk */
+  const uint64_t CHUNK = prove_chunk_labels();
   const uint64_t chunk_lab = std::min(CHUNK, num_labels);
   uint8_t *d_labels[2] = {nullptr, nullptr};
   uint8_t *h_labels[2] = {nullptr, nullptr};
@@ -1175,7 +1188,7 @@ int post_prove_scan(const uint8_t *labels, uint64_t count,
   } while (0)
   HIP_TRY(hipMalloc(&d_rk, rk.size() * 4));
   HIP_TRY(hipMemcpy(d_rk, rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
-  const uint64_t CHUNK = 1ull << 24;
+  const uint64_t CHUNK = prove_chunk_labels();
   HIP_TRY(hipMalloc(&d_labels, std::min(CHUNK, count) * 16));
   HIP_TRY(hipMalloc(&d_hits, sizeof(PostScanHit) * cap));
   HIP_TRY(hipMalloc(&d_hit_count, 4));

@@ -1154,6 +1154,18 @@ uint64_t poste_label_resident_slots(uint32_t gap_shift) {
   return (uint64_t)blocks_per_cu * cus * (POSTE_THREADS / 4);
 }
 
+/* POST_SCAN_MAX_BLOCKS lowers a scan variant's block cap (never raises it,
+ * never below 1; unset, zero or unparsable = the variant's own cap).  With
+ * a cap of a few blocks a few thousand labels already make every ILP chain
+ * live and the grid-stride loop iterate — what mainnet's 2^24-label chunks
+ * do at the full grid — so tests reach those paths at small sizes. */
+static uint32_t scan_block_cap(uint32_t variant_cap) {
+  const char *e = getenv("POST_SCAN_MAX_BLOCKS");
+  if (!e) return variant_cap;
+  long v = strtol(e, nullptr, 10);
+  return v >= 1 && v < (long)variant_cap ? (uint32_t)v : variant_cap;
+}
+
 hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
                                     uint32_t blocks, hipStream_t stream) {
   /* POST_SCAN_MODE: shared = round-1 shared-T-table kernel; tt4 =
@@ -1162,6 +1174,8 @@ hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
    * batched-gather scheduling; default = bank-replicated Te0 at 256.
    * Read per launch (launches are ms-scale) so tests can A/B kernels
    * within one process. */
+  const uint32_t cap = scan_block_cap(8192);
+  if (blocks > cap) blocks = cap;
   const char *e = getenv("POST_SCAN_MODE");
   const char *m = e ? e : "tt4"; /* fastest measured (r2d sweep); falls
                                     back to bankrep without 128 KiB LDS */
@@ -1180,7 +1194,8 @@ hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
     }();
     if (attr_ok) {
       uint32_t b4 = (uint32_t)((args->count + 1023) / 1024);
-      if (b4 > 2048) b4 = 2048;
+      const uint32_t cap4 = scan_block_cap(2048);
+      if (b4 > cap4) b4 = cap4;
       if (b4 == 0) b4 = 1;
       hipLaunchKernelGGL(post_scan_tt4_kernel, dim3(b4), dim3(1024),
                          32768 * 4, stream, *args);
@@ -1193,7 +1208,8 @@ hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
   size_t lds = 8192 * 4; /* 32 bank-strided copies of Te0 */
   if (wide) {
     uint32_t b5 = (uint32_t)((args->count + 511) / 512);
-    if (b5 > 4096) b5 = 4096;
+    const uint32_t cap5 = scan_block_cap(4096);
+    if (b5 > cap5) b5 = cap5;
     if (b5 == 0) b5 = 1;
     if (bg)
       hipLaunchKernelGGL((post_scan_bankrep_kernel<512, true>), dim3(b5),

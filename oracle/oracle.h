@@ -19,7 +19,9 @@
  *    hashlib.scrypt (OpenSSL) at the exact post parameters.
  *  - SHA-256 / HMAC: PINNED vs Python hashlib/hmac.
  *  - AES-128: PINNED vs FIPS-197 appendix C.1 vector; S-box derived
- *    algebraically (GF(2^8) inverse + affine), not transcribed.
+ *    algebraically (GF(2^8) inverse + affine), not transcribed.  The
+ *    inverse cipher is pinned by the same vector backwards and by
+ *    dec(enc(x)) == x on random blocks.
  *  - BLAKE3: pinned by the two official test vectors known to the builders
  *    (empty input, 1-byte input) + an independent second implementation in
  *    the engine (go-spacemesh_amd/csrc/blake3_impl.h) that must agree on
@@ -71,6 +73,10 @@ void oracle_blake3(const uint8_t *msg, size_t len, uint8_t out[32]);
 void oracle_blake3_xof(const uint8_t *msg, size_t len,
                        uint8_t *out, size_t outlen);
 void oracle_aes128_enc_block(const uint8_t key[16], const uint8_t in[16],
+                             uint8_t out[16]);
+/* FIPS-197 inverse cipher; lets a test choose a ciphertext and derive the
+ * label that encrypts to it. */
+void oracle_aes128_dec_block(const uint8_t key[16], const uint8_t in[16],
                              uint8_t out[16]);
 
 /* ---------- POST semantics ---------- */
@@ -150,6 +156,29 @@ int oracle_prove(const uint8_t *labels, uint64_t num_labels,
                  uint32_t k1, uint32_t k2, uint32_t nonces,
                  const uint8_t pow_difficulty[32],
                  OracleProof *proof);
+
+typedef struct {
+  uint64_t index;
+  uint32_t nonce;
+  uint32_t pad;
+} OracleScanHit;
+
+/* The raw hit stream behind oracle_prove, for one label range: `labels`
+ * holds `count` 16-byte labels whose first label has index `index_base`,
+ * out of `total_labels` in the whole space (which sets the difficulty).
+ * Emits every (index_base + i, 2c + j) with
+ *   LE64(AES_key_c(label_i)[8j..8j+8)) < oracle_proving_difficulty(k1,
+ *   total_labels),
+ * sorted by (index, nonce).  group_pows holds one k2pow per nonce group.
+ * *n_out is the number of hits found; only the first `cap` are written, so
+ * a caller that gets *n_out > cap calls again with more room.  Returns 0,
+ * or -1 on bad `nonces` or allocation failure.  Multi-threaded over OpenMP
+ * when built with it. */
+int oracle_scan_hits(const uint8_t *labels, uint64_t count,
+                     uint64_t index_base, uint64_t total_labels,
+                     const uint8_t challenge[32], uint32_t k1,
+                     uint32_t nonces, const uint64_t *group_pows,
+                     OracleScanHit *hits_out, uint64_t cap, uint64_t *n_out);
 
 /* Verification inputs mirror shared.ProofMetadata as assembled at
  * activation/validation.go:193-199. */

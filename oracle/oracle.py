@@ -46,6 +46,10 @@ class VrfNonce(ctypes.Structure):
     _fields_ = [("index", c_uint64), ("label", c_uint8 * 32), ("found", c_int)]
 
 
+class ScanHit(ctypes.Structure):
+    _fields_ = [("index", c_uint64), ("nonce", c_uint32), ("pad", c_uint32)]
+
+
 def _build_if_needed() -> None:
     if not os.path.exists(_LIB_PATH):
         subprocess.run(["make", "-C", _DIR], check=True, capture_output=True)
@@ -72,6 +76,13 @@ def load() -> ctypes.CDLL:
                                      ctypes.c_char_p, c_size_t]),
         "oracle_aes128_enc_block": (None, [ctypes.c_char_p, ctypes.c_char_p,
                                            ctypes.c_char_p]),
+        "oracle_aes128_dec_block": (None, [ctypes.c_char_p, ctypes.c_char_p,
+                                           ctypes.c_char_p]),
+        "oracle_scan_hits": (c_int, [ctypes.c_char_p, c_uint64, c_uint64,
+                                     c_uint64, ctypes.c_char_p, c_uint32,
+                                     c_uint32, POINTER(c_uint64),
+                                     POINTER(ScanHit), c_uint64,
+                                     POINTER(c_uint64)]),
         "oracle_commitment": (None, [ctypes.c_char_p, ctypes.c_char_p,
                                      ctypes.c_char_p]),
         "oracle_label": (c_int, [ctypes.c_char_p, c_uint64, c_uint32,
@@ -153,6 +164,11 @@ class Oracle:
         self.lib.oracle_aes128_enc_block(key, block, out)
         return out.raw
 
+    def aes128_dec(self, key: bytes, block: bytes) -> bytes:
+        out = create_string_buffer(16)
+        self.lib.oracle_aes128_dec_block(key, block, out)
+        return out.raw
+
     # POST ------------------------------------------------------------------
     def commitment(self, node_id: bytes, atx_id: bytes) -> bytes:
         out = create_string_buffer(32)
@@ -186,6 +202,37 @@ class Oracle:
         if rc:
             raise ValueError("prove found no nonce")
         return proof
+
+    def cipher_key(self, challenge: bytes, cipher: int,
+                   group_pow: int) -> bytes:
+        out = create_string_buffer(16)
+        self.lib.oracle_prove_cipher_key(challenge, cipher, group_pow, out)
+        return out.raw
+
+    def scan_hits(self, labels: bytes, index_base: int, total_labels: int,
+                  challenge: bytes, k1: int, nonces: int, pows):
+        """Every (index, nonce) hit of the proving scan over `labels`,
+        sorted by (index, nonce)."""
+        count = len(labels) // LABEL_SIZE
+        parr = (c_uint64 * len(pows))(*pows)
+        diff = self.lib.oracle_proving_difficulty(k1, total_labels)
+        # room for the expected number of hits; a second call if it was short
+        cap = int(count * nonces * (diff + 1) / 2.0**64 * 1.25) + 1024
+        while True:
+            hits = (ScanHit * cap)()
+            n = c_uint64(0)
+            rc = self.lib.oracle_scan_hits(labels, count, index_base,
+                                           total_labels, challenge, k1,
+                                           nonces, parr, hits, cap, byref(n))
+            if rc:
+                raise ValueError("scan_hits failed")
+            if n.value <= cap:
+                break
+            cap = n.value
+        import numpy as np
+        arr = np.frombuffer(hits, dtype=[("index", "<u8"), ("nonce", "<u4"),
+                                         ("pad", "<u4")], count=n.value)
+        return list(zip(arr["index"].tolist(), arr["nonce"].tolist()))
 
     def verify(self, proof: Proof, meta: ProofMetadata, scrypt_n: int,
                k1: int, k2: int, k3: int, subset_seed: bytes | None,

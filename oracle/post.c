@@ -269,6 +269,90 @@ int oracle_prove(const uint8_t *labels, uint64_t num_labels,
   return rc;
 }
 
+/* The full hit stream of the proving scan over one label range, with the
+ * same primitives and predicate as oracle_prove.  Each thread takes one
+ * contiguous slice of the range and the slices are concatenated in order,
+ * so the output is sorted by (index, nonce) whatever the thread count. */
+int oracle_scan_hits(const uint8_t *labels, uint64_t count,
+                     uint64_t index_base, uint64_t total_labels,
+                     const uint8_t challenge[32], uint32_t k1,
+                     uint32_t nonces, const uint64_t *group_pows,
+                     OracleScanHit *hits_out, uint64_t cap, uint64_t *n_out) {
+  if (nonces == 0 || nonces % ORACLE_NONCE_GROUP != 0) return -1;
+  uint32_t n_ciphers = nonces / ORACLE_NONCES_PER_AES;
+  uint64_t difficulty = oracle_proving_difficulty(k1, total_labels);
+
+  uint8_t(*keys)[16] = malloc((size_t)n_ciphers * 16);
+  for (uint32_t c = 0; c < n_ciphers; c++) {
+    uint32_t grp = (c * ORACLE_NONCES_PER_AES) / ORACLE_NONCE_GROUP;
+    oracle_prove_cipher_key(challenge, c, group_pows[grp], keys[c]);
+  }
+  /* the AES S-box is built lazily on first use: do that on one thread */
+  uint8_t warm[16];
+  oracle_aes128_enc_block(keys[0], keys[0], warm);
+
+  int n_slices = 1;
+#ifdef _OPENMP
+  n_slices = omp_get_max_threads();
+#endif
+  if (n_slices < 1) n_slices = 1;
+  OracleScanHit **part = calloc((size_t)n_slices, sizeof(*part));
+  uint64_t *part_n = calloc((size_t)n_slices, sizeof(uint64_t));
+  int err = 0;
+
+#pragma omp parallel for schedule(static, 1)
+  for (int s = 0; s < n_slices; s++) {
+    uint64_t lo = count / (uint64_t)n_slices * (uint64_t)s;
+    uint64_t hi = s == n_slices - 1 ? count
+                                    : count / (uint64_t)n_slices *
+                                          (uint64_t)(s + 1);
+    uint64_t room = 0, n = 0;
+    OracleScanHit *buf = NULL;
+    for (uint64_t i = lo; i < hi; i++) {
+      const uint8_t *lbl = labels + i * ORACLE_LABEL_SIZE;
+      for (uint32_t c = 0; c < n_ciphers; c++) {
+        uint8_t out[16];
+        oracle_aes128_enc_block(keys[c], lbl, out);
+        for (int j = 0; j < ORACLE_NONCES_PER_AES; j++) {
+          uint64_t v = 0;
+          for (int b = 0; b < 8; b++)
+            v |= (uint64_t)out[8 * j + b] << (8 * b);
+          if (v >= difficulty) continue;
+          if (n == room) {
+            room = room ? room * 2 : 1024;
+            OracleScanHit *nb = realloc(buf, room * sizeof(*nb));
+            if (!nb) {
+#pragma omp atomic write
+              err = -1;
+              room = n;
+              continue;
+            }
+            buf = nb;
+          }
+          buf[n].index = index_base + i;
+          buf[n].nonce = c * ORACLE_NONCES_PER_AES + (uint32_t)j;
+          buf[n].pad = 0;
+          n++;
+        }
+      }
+    }
+    part[s] = buf;
+    part_n[s] = n;
+  }
+
+  uint64_t total = 0;
+  for (int s = 0; s < n_slices; s++) {
+    for (uint64_t k = 0; k < part_n[s]; k++, total++)
+      if (total < cap) hits_out[total] = part[s][k];
+    free(part[s]);
+  }
+  *n_out = total;
+  free(part);
+  free(part_n);
+  free(keys);
+  return err;
+}
+
 int oracle_verify(const OracleProof *proof, const OracleProofMetadata *meta,
                   uint32_t scrypt_n, uint32_t k1, uint32_t k2, uint32_t k3,
                   const uint8_t *subset_seed, size_t subset_seed_len,

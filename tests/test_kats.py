@@ -83,6 +83,24 @@ def test_aes128_fips197(oracle):
         assert got.hex() == v["ct"]
 
 
+def test_aes128_dec_fips197(oracle):
+    """FIPS-197 Appendix C.1 in both directions: the inverse cipher takes
+    the ciphertext back to the plaintext, and the pair is the encryptor's."""
+    for v in GOLDEN["aes128_fips197"]:
+        key, pt, ct = (bytes.fromhex(v[k]) for k in ("key", "pt", "ct"))
+        assert oracle.aes128_dec(key, ct) == pt
+        assert oracle.aes128(key, oracle.aes128_dec(key, ct)) == ct
+
+
+def test_aes128_dec_inverts_enc_random(oracle):
+    rng = random.Random(5)
+    for _ in range(1000):
+        key = bytes(rng.randrange(256) for _ in range(16))
+        x = bytes(rng.randrange(256) for _ in range(16))
+        assert oracle.aes128_dec(key, oracle.aes128(key, x)) == x
+        assert oracle.aes128(key, oracle.aes128_dec(key, x)) == x
+
+
 def test_label_golden_openssl(oracle):
     lv = GOLDEN["labels_openssl"]
     commitment = oracle.commitment(bytes.fromhex(lv["node_id"]),

@@ -66,6 +66,44 @@ def test_merge_matches_oracle_prover(oracle, setup):
     assert merged.indices == bytes(op.indices[:op.indices_len])
 
 
+def test_scan_hits_matches_python_loop(oracle, setup):
+    """oracle_scan_hits (the C hit stream the GPU scan tests compare
+    against) == the pure-Python loop above, in (index, nonce) order, for a
+    whole range and for a sub-range with a non-zero index base."""
+    labels, total = setup
+    K1, NONCES = 12, 16
+    pows = [oracle.lib.oracle_k2pow(CHALLENGE, g, POW_DIFF)
+            for g in range(NONCES // 16)]
+    want = oracle_hits(oracle, labels, total, K1, NONCES, pows)
+    assert want == sorted(want) and len(want) > NONCES
+    got = oracle.scan_hits(labels, 0, total, CHALLENGE, K1, NONCES, pows)
+    assert got == want
+    lo, hi = 37, 201
+    part = oracle.scan_hits(labels[lo * 16:hi * 16], lo, total, CHALLENGE,
+                            K1, NONCES, pows)
+    assert part == [h for h in want if lo <= h[0] < hi]
+    # a difficulty that most values pass: many hits per label, 2 groups
+    pows2 = [oracle.lib.oracle_k2pow(CHALLENGE, g, POW_DIFF)
+             for g in range(2)]
+    want2 = oracle_hits(oracle, labels, total, total // 2, 32, pows2)
+    assert len(want2) > total * 8
+    assert oracle.scan_hits(labels, 0, total, CHALLENGE, total // 2, 32,
+                            pows2) == want2
+
+
+def test_merge_of_scan_hits_matches_oracle_prover(oracle, setup):
+    labels, total = setup
+    K1, K2, NONCES = 12, 8, 16
+    op = oracle.prove(labels, total, CHALLENGE, K1, K2, NONCES, POW_DIFF)
+    pows = [oracle.lib.oracle_k2pow(CHALLENGE, g, POW_DIFF)
+            for g in range(NONCES // 16)]
+    hits = oracle.scan_hits(labels, 0, total, CHALLENGE, K1, NONCES, pows)
+    merged = proving.merge_shards([hits], NONCES, K2, total, pows)
+    assert merged is not None
+    assert (merged.nonce, merged.pow) == (op.nonce, op.pow)
+    assert merged.indices == bytes(op.indices[:op.indices_len])
+
+
 def test_merge_no_winner(oracle):
     assert proving.merge_shards([[], []], 16, 8, 256, [0]) is None
     # fewer than k2 hits for every nonce
