@@ -17,6 +17,8 @@ from .verifier_pool import (  # noqa: F401
     OffloadingVerifier,
 )
 from .api import (  # noqa: F401
+    AuditOpts,
+    AuditReport,
     Engine,
     EngineError,
     PostConfig,
@@ -28,10 +30,14 @@ from .api import (  # noqa: F401
     ProveOpts,
     VerifyOpts,
     load_engine,
+    sample_indices,
+    verify_data,
+    verify_data_buffer,
 )
 
 __all__ = [
-    "BatchingVerifier", "Engine", "EngineError", "OffloadingVerifier", "PostConfig", "PostProof",
+    "AuditOpts", "AuditReport", "BatchingVerifier", "Engine", "EngineError", "OffloadingVerifier", "PostConfig", "PostProof",
     "PostProofMetadata", "PostSetupManager", "PostSetupOpts", "PostVerifier",
-    "ProveOpts", "VerifyOpts", "events", "load_engine",
+    "ProveOpts", "VerifyOpts", "events", "load_engine", "sample_indices",
+    "verify_data", "verify_data_buffer",
 ]

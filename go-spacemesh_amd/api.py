@@ -98,6 +98,26 @@ class _CVerifyConfig(ctypes.Structure):
                 ("scrypt_n", c_uint32), ("provider_id", c_uint32)]
 
 
+class _CAuditConfig(ctypes.Structure):
+    _fields_ = [("provider_id", c_uint32), ("sample_every", c_uint64),
+                ("seed", c_uint64), ("index_start", c_uint64),
+                ("index_end", c_uint64), ("scratch_bytes", c_uint64),
+                ("progress", c_void_p), ("user", c_void_p)]
+
+
+class _CBadLabel(ctypes.Structure):
+    _fields_ = [("index", c_uint64), ("on_disk", c_uint8 * 16),
+                ("expected", c_uint8 * 16)]
+
+
+class _CAuditReport(ctypes.Structure):
+    _fields_ = [("labels_in_range", c_uint64), ("labels_sampled", c_uint64),
+                ("labels_checked", c_uint64), ("labels_missing", c_uint64),
+                ("labels_bad", c_uint64)]
+
+
+_AUDIT_PROGRESS = ctypes.CFUNCTYPE(c_int, c_void_p, c_uint64, c_uint64)
+
 _lib_lock = threading.Lock()
 _lib: Optional[ctypes.CDLL] = None
 
@@ -154,6 +174,16 @@ def load_engine() -> ctypes.CDLL:
                 POINTER(c_int), POINTER(c_uint32)]),
             "post_verify_vrf_nonce": (c_int, [POINTER(CProofMetadata),
                                               c_uint64, c_uint32, c_uint32]),
+            "post_verify_data_sample": (c_int, [
+                c_uint64, c_uint64, c_uint64, c_uint64, c_uint64,
+                POINTER(c_uint64), c_uint32, POINTER(c_uint32)]),
+            "post_verify_data": (c_int, [c_char_p, POINTER(_CAuditConfig),
+                                         POINTER(_CBadLabel), c_uint32,
+                                         POINTER(_CAuditReport)]),
+            "post_verify_data_buffer": (c_int, [
+                ctypes.c_char_p, c_uint64, c_uint64, ctypes.c_char_p,
+                ctypes.c_char_p, c_uint32, POINTER(_CAuditConfig),
+                POINTER(_CBadLabel), c_uint32, POINTER(_CAuditReport)]),
             "post_selftest_blake3": (None, [ctypes.c_char_p, c_size_t,
                                             ctypes.c_char_p]),
             "post_selftest_aes128": (None, [ctypes.c_char_p, ctypes.c_char_p,
@@ -213,6 +243,34 @@ class VerifyOpts:
     subset_seed: Optional[bytes] = None
     selected_index: int = -1
     provider_id: int = 0
+
+
+@dataclasses.dataclass
+class AuditOpts:
+    """Postdata audit (verify-data): one label per window of `sample_every`
+    labels is recomputed and compared with the bytes on disk."""
+    sample_every: int = 100             # 1 % of the labels
+    seed: int = 0
+    index_start: int = 0                # 0,0 = the whole space / buffer
+    index_end: int = 0
+    provider_id: int = 0
+    scratch_bytes: int = 0
+    max_report: int = 64                # mismatches returned in detail
+
+
+@dataclasses.dataclass
+class AuditReport:
+    labels_in_range: int
+    labels_sampled: int
+    labels_checked: int
+    labels_missing: int
+    labels_bad: int                     # the full count, whatever max_report
+    # (index, on_disk, expected) of the max_report smallest bad indices
+    bad: list = dataclasses.field(default_factory=list)
+
+    @property
+    def clean(self) -> bool:
+        return self.labels_bad == 0 and self.labels_missing == 0
 
 
 @dataclasses.dataclass
@@ -540,3 +598,90 @@ class PostVerifier:
         rc = self.engine.lib.post_verify_vrf_nonce(byref(meta.to_c()), index,
                                                    self.scrypt_n, provider_id)
         self.engine._check(rc)
+
+
+# ------------------------- postdata audit -------------------------
+
+def sample_indices(seed: int, sample_every: int, index_start: int,
+                   index_end: int, first_window: int = 0,
+                   max_count: Optional[int] = None) -> list:
+    """The audit's sampled indices (host-only, needs no GPU): one per window
+    of `sample_every` labels of [index_start, index_end), starting at window
+    `first_window`, at most `max_count` of them (default: to the end)."""
+    eng = Engine()
+    mask = (1 << 64) - 1
+    out = []
+    left = max_count
+    while left is None or left > 0:
+        page = 1 << 16 if left is None else min(left, 1 << 16)
+        buf = (c_uint64 * page)()
+        n = c_uint32(0)
+        eng._check(eng.lib.post_verify_data_sample(
+            seed & mask, sample_every, index_start, index_end,
+            first_window + len(out), buf, page, byref(n)))
+        out.extend(buf[:n.value])
+        if n.value < page:
+            break
+        if left is not None:
+            left -= n.value
+    return out
+
+
+def _audit_call(opts: Optional[AuditOpts], progress, call) -> AuditReport:
+    eng = Engine()
+    if opts is None:
+        opts = AuditOpts()
+    ac = _CAuditConfig()
+    ac.provider_id = opts.provider_id
+    ac.sample_every = opts.sample_every
+    ac.seed = opts.seed & ((1 << 64) - 1)
+    ac.index_start = opts.index_start
+    ac.index_end = opts.index_end
+    ac.scratch_bytes = opts.scratch_bytes
+    cb = None
+    raised = []
+    if progress is not None:
+        # a truthy return from progress(checked, to_check) stops the audit;
+        # so does an exception, which is re-raised once the engine returns
+        def trampoline(_user, checked, to_check):
+            try:
+                return 1 if progress(checked, to_check) else 0
+            except BaseException as e:  # noqa: BLE001
+                raised.append(e)
+                return 1
+        cb = _AUDIT_PROGRESS(trampoline)
+        ac.progress = ctypes.cast(cb, c_void_p)
+    cap = max(0, opts.max_report)
+    bad = (_CBadLabel * cap)() if cap else None
+    rep = _CAuditReport()
+    rc = call(eng.lib, byref(ac), bad, cap, byref(rep))
+    if raised:
+        raise raised[0]
+    eng._check(rc)
+    found = [(bad[i].index, bytes(bad[i].on_disk), bytes(bad[i].expected))
+             for i in range(min(cap, rep.labels_bad))]
+    return AuditReport(rep.labels_in_range, rep.labels_sampled,
+                       rep.labels_checked, rep.labels_missing,
+                       rep.labels_bad, found)
+
+
+def verify_data(data_dir: str, opts: Optional[AuditOpts] = None,
+                progress=None) -> AuditReport:
+    """Audit the labels of a postdata directory against its own metadata.
+    Corruption is reported through the AuditReport, not raised."""
+    return _audit_call(
+        opts, progress,
+        lambda lib, ac, bad, cap, rep: lib.post_verify_data(
+            data_dir.encode(), ac, bad, cap, rep))
+
+
+def verify_data_buffer(labels: bytes, index_base: int, node_id: bytes,
+                       atx_id: bytes, scrypt_n: int,
+                       opts: Optional[AuditOpts] = None,
+                       progress=None) -> AuditReport:
+    """Audit a host buffer holding labels [index_base, index_base + n)."""
+    return _audit_call(
+        opts, progress,
+        lambda lib, ac, bad, cap, rep: lib.post_verify_data_buffer(
+            labels, len(labels) // LABEL_SIZE, index_base, node_id, atx_id,
+            scrypt_n, ac, bad, cap, rep))

@@ -14,14 +14,17 @@
 
 #include <hip/hip_runtime.h>
 
+#include <fcntl.h>
 #include <sys/stat.h>
 #include <sys/types.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <array>
 #include <atomic>
 #include <thread>
 #include <chrono>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1304,6 +1307,526 @@ int post_prove(const char *data_dir, const PostProveConfig *cfg,
     return POST_OK;
   };
   return prove_core(reader, total, cfg, out);
+}
+
+/* ------------------------- postdata audit ------------------------- */
+
+static inline uint64_t splitmix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+static inline uint64_t audit_windows(uint64_t range, uint64_t k) {
+  return range / k + (range % k ? 1 : 0);
+}
+
+/* The sampling rule: window w of [index_start, index_end)
+ * contributes first + h % len with first = index_start + w*K,
+ * len = min(K, index_end - first), h = splitmix64(splitmix64(seed) + w).
+ * h % len favours some offsets by at most len / 2^64, below 2^-20 even for
+ * a window of 2^44 labels: modulo bias is irrelevant at these sizes. */
+int post_verify_data_sample(uint64_t seed, uint64_t sample_every,
+                            uint64_t index_start, uint64_t index_end,
+                            uint64_t first_window, uint64_t *out,
+                            uint32_t cap, uint32_t *n) {
+  if (!n || (cap && !out)) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  *n = 0;
+  if (sample_every == 0 || index_start >= index_end) {
+    set_error("sample_every must be >= 1 and the range non-empty");
+    return POST_ERR_INVALID_ARGS;
+  }
+  const uint64_t windows =
+      audit_windows(index_end - index_start, sample_every);
+  const uint64_t s = splitmix64(seed);
+  uint32_t got = 0;
+  for (uint64_t w = first_window; w < windows && got < cap; w++, got++) {
+    const uint64_t first = index_start + w * sample_every;
+    const uint64_t len = std::min(sample_every, index_end - first);
+    out[got] = first + splitmix64(s + w) % len;
+  }
+  *n = got;
+  return POST_OK;
+}
+
+/* label source of an audit batch: for the n ascending sampled indices idx,
+ * append the labels that exist to (out_idx, out_lab) and set *n_out; the
+ * rest are missing */
+using AuditGather =
+    std::function<int(const uint64_t *idx, uint32_t n, uint64_t *out_idx,
+                      uint8_t *out_lab, uint32_t *n_out)>;
+
+/* Up to this period the audit reads the covering span sequentially and
+ * picks the sampled labels from it (every 4-KiB page of 256 labels is
+ * touched anyway); above it, one pread per sample. */
+constexpr uint64_t AUDIT_SEQ_MAX_K = 256;
+constexpr size_t AUDIT_SEQ_CHUNK = 4u << 20;
+
+/* postdata_*.bin reader of an audit: one descriptor stays open while the
+ * (ascending) samples are inside a file; chunk is the read-ahead. */
+struct AuditDirReader {
+  std::string dir;
+  uint64_t per_file = 1;
+  size_t chunk = POST_LABEL_SIZE;
+  int fd = -1;
+  uint64_t file_i = UINT64_MAX;
+  uint64_t file_bytes = 0;
+  std::vector<uint8_t> buf;
+  uint64_t buf_off = 0;
+  size_t buf_len = 0;
+
+  ~AuditDirReader() {
+    if (fd >= 0) ::close(fd);
+  }
+
+  /* 1 = label copied, 0 = missing (file absent or ends before the label's
+   * 16th byte), -1 = IO error (set_error called) */
+  int fetch(uint64_t g, uint8_t *dst) {
+    const uint64_t fi = g / per_file;
+    const uint64_t off = (g % per_file) * POST_LABEL_SIZE;
+    if (fi != file_i) {
+      if (fd >= 0) ::close(fd);
+      fd = -1;
+      file_i = fi;
+      file_bytes = 0;
+      buf_len = 0;
+      /* a std::string: a long data dir must not be cut short and then
+       * read as "file absent" */
+      const std::string path = dir + "/postdata_" +
+                               std::to_string((unsigned long long)fi) + ".bin";
+      fd = ::open(path.c_str(), O_RDONLY);
+      if (fd < 0 && errno != ENOENT) {
+        set_error("cannot open " + path);
+        return -1;
+      }
+      if (fd >= 0) {
+        struct stat st;
+        if (::fstat(fd, &st) != 0) {
+          set_error("cannot stat " + path);
+          return -1;
+        }
+        file_bytes = (uint64_t)st.st_size;
+      }
+    }
+    if (fd < 0 || off + POST_LABEL_SIZE > file_bytes) return 0;
+    if (off < buf_off || off + POST_LABEL_SIZE > buf_off + buf_len) {
+      const size_t want =
+          (size_t)std::min<uint64_t>(chunk, file_bytes - off);
+      if (buf.size() < want) buf.resize(want);
+      size_t got = 0;
+      while (got < want) {
+        ssize_t r = ::pread(fd, buf.data() + got, want - got,
+                            (off_t)(off + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) break;
+        got += (size_t)r;
+      }
+      if (got < POST_LABEL_SIZE) {
+        set_error("short read from postdata file " +
+                  std::to_string((unsigned long long)fi));
+        return -1;
+      }
+      buf_off = off;
+      buf_len = got;
+    }
+    std::memcpy(dst, buf.data() + (off - buf_off), POST_LABEL_SIZE);
+    return 1;
+  }
+};
+
+/* Shared by post_verify_data and post_verify_data_buffer, which validate
+ * their arguments first: [start, end) is non-empty and sample_every >= 1.
+ * Batches go in ascending index order; the host gathers batch i+1 while the
+ * GPU runs batch i (the prove_core pattern).  Nothing here is global: every
+ * buffer and stream belongs to the call. */
+static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
+                      uint32_t scrypt_n, uint64_t start, uint64_t end,
+                      const PostAuditConfig *cfg, PostBadLabel *bad,
+                      uint32_t cap, PostAuditReport *report) {
+  int rc = require_gpu(cfg->provider_id);
+  if (rc != POST_OK) return rc;
+
+  /* POST_AUDIT_DEBUG: where a call's wall time went (stderr) */
+  const bool dbg = getenv("POST_AUDIT_DEBUG") != nullptr;
+  auto tick = [] {
+    return std::chrono::duration<double>(
+               std::chrono::steady_clock::now().time_since_epoch())
+        .count();
+  };
+  const double t_start = tick();
+  double t_gather = 0, t_drain = 0;
+
+  const uint64_t windows = audit_windows(end - start, cfg->sample_every);
+  std::memset(report, 0, sizeof(*report));
+  report->labels_in_range = end - start;
+  report->labels_sampled = windows;
+
+  /* lanes and batch exactly as post_init_new sizes them */
+  const uint32_t gap_shift = pick_gap_shift(scrypt_n);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  uint64_t budget = cfg->scratch_bytes ? cfg->scratch_bytes
+                                       : (uint64_t)((double)free_b * 0.80);
+  const uint64_t per_lane = ((uint64_t)scrypt_n >> gap_shift) * 128;
+  uint64_t lanes = budget / per_lane;
+  lanes = std::min<uint64_t>(lanes, std::max<uint64_t>(windows, 64));
+  lanes = std::min<uint64_t>(lanes, poste_label_resident_slots(gap_shift));
+  lanes = (lanes / 128) * 128;
+  if (lanes == 0) lanes = 128;
+  const uint64_t batch = std::min<uint64_t>(windows, lanes * 4);
+  const uint32_t blocks = (uint32_t)(lanes / 64); /* 64 quads/block */
+
+  uint32_t *d_scratch = nullptr, *d_xbuf = nullptr;
+  uint64_t *d_idx[2] = {nullptr, nullptr}, *h_idx[2] = {nullptr, nullptr};
+  uint8_t *d_exp[2] = {nullptr, nullptr}, *h_exp[2] = {nullptr, nullptr};
+  PostAuditMismatch *d_mis[2] = {nullptr, nullptr};
+  unsigned int *d_count[2] = {nullptr, nullptr};
+  unsigned int *h_count = nullptr; /* pinned, one per parity */
+  hipEvent_t done[2] = {nullptr, nullptr};
+  hipStream_t stream = nullptr, copy_stream = nullptr;
+  auto cleanup = [&] {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (int p = 0; p < 2; p++) {
+      if (d_idx[p]) (void)hipFree(d_idx[p]);
+      if (h_idx[p]) (void)hipHostFree(h_idx[p]);
+      if (d_exp[p]) (void)hipFree(d_exp[p]);
+      if (h_exp[p]) (void)hipHostFree(h_exp[p]);
+      if (d_mis[p]) (void)hipFree(d_mis[p]);
+      if (d_count[p]) (void)hipFree(d_count[p]);
+      if (done[p]) (void)hipEventDestroy(done[p]);
+    }
+    if (h_count) (void)hipHostFree(h_count);
+    if (d_scratch) (void)hipFree(d_scratch);
+    if (d_xbuf) (void)hipFree(d_xbuf);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (copy_stream) (void)hipStreamDestroy(copy_stream);
+  };
+#undef HIP_TRY
+#define HIP_TRY(expr)                                                          \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) {                                                    \
+      cleanup();                                                               \
+      return hip_fail(#expr, _e);                                              \
+    }                                                                          \
+  } while (0)
+  HIP_TRY(hipStreamCreate(&stream));
+  HIP_TRY(hipStreamCreate(&copy_stream));
+  HIP_TRY(hipMalloc(&d_scratch, (size_t)lanes * per_lane));
+  HIP_TRY(hipMalloc(&d_xbuf, (size_t)batch * 128));
+  HIP_TRY(hipHostMalloc(&h_count, 2 * sizeof(unsigned int)));
+  for (int p = 0; p < 2; p++) {
+    HIP_TRY(hipMalloc(&d_idx[p], (size_t)batch * 8));
+    HIP_TRY(hipHostMalloc(&h_idx[p], (size_t)batch * 8));
+    HIP_TRY(hipMalloc(&d_exp[p], (size_t)batch * POST_LABEL_SIZE));
+    HIP_TRY(hipHostMalloc(&h_exp[p], (size_t)batch * POST_LABEL_SIZE));
+    HIP_TRY(hipMalloc(&d_mis[p], (size_t)batch * sizeof(PostAuditMismatch)));
+    HIP_TRY(hipMalloc(&d_count[p], sizeof(unsigned int)));
+    HIP_TRY(hipEventCreate(&done[p]));
+  }
+
+  const double t_alloc = tick() - t_start;
+
+  AuditKernelArgs aa;
+  std::memset(&aa, 0, sizeof(aa));
+  load_commitment_words(commitment, aa.label.commitment_le);
+  aa.label.scrypt_n = scrypt_n;
+  aa.label.gap_shift = gap_shift;
+  aa.label.scratch = d_scratch;
+  aa.label.scratch_lanes = lanes;
+  aa.label.xbuf = d_xbuf;
+
+  std::vector<uint64_t> sample((size_t)batch);
+  std::vector<PostAuditMismatch> mis;
+  uint32_t in_batch[2] = {0, 0}; /* labels sent to the GPU per parity */
+  uint32_t kept = 0;
+
+  /* collect a launched batch: mismatches ascending, then progress */
+  auto drain = [&](int p) -> int {
+    const uint32_t n = in_batch[p];
+    if (n) {
+      hipError_t e = hipEventSynchronize(done[p]);
+      if (e != hipSuccess) return hip_fail("hipEventSynchronize", e);
+      const unsigned int n_bad = h_count[p];
+      if (n_bad > n) {
+        set_error("audit mismatch count exceeds the batch");
+        return POST_ERR;
+      }
+      if (n_bad) {
+        mis.resize(n_bad);
+        /* its own stream: the next batch is already queued on `stream` */
+        e = hipMemcpyAsync(mis.data(), d_mis[p],
+                           sizeof(PostAuditMismatch) * n_bad,
+                           hipMemcpyDeviceToHost, copy_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(copy_stream);
+        if (e != hipSuccess) return hip_fail("audit mismatch copy", e);
+        std::sort(mis.begin(), mis.end(),
+                  [](const PostAuditMismatch &x, const PostAuditMismatch &y) {
+                    return x.index < y.index;
+                  });
+        for (unsigned int i = 0; i < n_bad && kept < cap; i++, kept++) {
+          const uint64_t *at =
+              std::lower_bound(h_idx[p], h_idx[p] + n, (uint64_t)mis[i].index);
+          if (at == h_idx[p] + n || *at != mis[i].index) {
+            set_error("audit mismatch names an index outside its batch");
+            return POST_ERR;
+          }
+          PostBadLabel &b = bad[kept];
+          b.index = mis[i].index;
+          std::memcpy(b.on_disk, h_exp[p] + (size_t)(at - h_idx[p]) *
+                                               POST_LABEL_SIZE,
+                      POST_LABEL_SIZE);
+          std::memcpy(b.expected, mis[i].label, POST_LABEL_SIZE);
+        }
+        report->labels_bad += n_bad;
+      }
+      report->labels_checked += n;
+    }
+    if (cfg->progress &&
+        cfg->progress(cfg->user, report->labels_checked, windows) != 0) {
+      set_error("audit cancelled by the progress callback");
+      return POST_ERR_CANCELLED;
+    }
+    return POST_OK;
+  };
+
+  int parity = 0;
+  bool have_prev = false;
+  for (uint64_t w = 0; w < windows; parity ^= 1) {
+    /* this parity's buffers are free: their batch was drained last turn */
+    const uint32_t nw = (uint32_t)std::min<uint64_t>(batch, windows - w);
+    uint32_t drawn = 0, present = 0;
+    double t0 = tick();
+    rc = post_verify_data_sample(cfg->seed, cfg->sample_every, start, end, w,
+                                 sample.data(), nw, &drawn);
+    if (rc == POST_OK)
+      rc = gather(sample.data(), drawn, h_idx[parity], h_exp[parity],
+                  &present);
+    t_gather += tick() - t0;
+    if (rc != POST_OK) {
+      cleanup();
+      return rc;
+    }
+    report->labels_missing += drawn - present;
+    in_batch[parity] = present;
+    if (present) {
+      HIP_TRY(hipMemcpyAsync(d_idx[parity], h_idx[parity], (size_t)present * 8,
+                             hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync(d_exp[parity], h_exp[parity],
+                             (size_t)present * POST_LABEL_SIZE,
+                             hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemsetAsync(d_count[parity], 0, sizeof(unsigned int),
+                             stream));
+      aa.label.count = present;
+      aa.label.indices = d_idx[parity];
+      aa.expected = (const uint4 *)d_exp[parity];
+      aa.mismatch = d_mis[parity];
+      aa.count = d_count[parity];
+      HIP_TRY(poste_launch_label_audit(&aa, blocks, stream));
+      HIP_TRY(hipMemcpyAsync(&h_count[parity], d_count[parity],
+                             sizeof(unsigned int), hipMemcpyDeviceToHost,
+                             stream));
+      HIP_TRY(hipEventRecord(done[parity], stream));
+    }
+    if (have_prev) {
+      t0 = tick();
+      rc = drain(parity ^ 1);
+      t_drain += tick() - t0;
+      if (rc != POST_OK) {
+        cleanup();
+        return rc;
+      }
+    }
+    have_prev = true;
+    w += nw;
+  }
+  {
+    const double t0 = tick();
+    rc = drain(parity ^ 1);
+    t_drain += tick() - t0;
+  }
+  const double t_loop_end = tick();
+#undef HIP_TRY
+#define HIP_TRY(expr)                                                          \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
+  } while (0)
+  cleanup();
+  if (dbg)
+    std::fprintf(stderr,
+                 "[audit] lanes=%llu batch=%llu windows=%llu alloc %.3fs "
+                 "gather %.3fs wait+collect %.3fs free %.3fs total %.3fs\n",
+                 (unsigned long long)lanes, (unsigned long long)batch,
+                 (unsigned long long)windows, t_alloc, t_gather, t_drain,
+                 tick() - t_loop_end, tick() - t_start);
+  return rc;
+}
+
+static int audit_check_args(const PostAuditConfig *cfg, PostBadLabel *bad,
+                            uint32_t cap, PostAuditReport *report) {
+  if (!cfg || !report || (cap && !bad)) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (cfg->sample_every == 0) {
+    set_error("sample_every must be >= 1");
+    return POST_ERR_INVALID_ARGS;
+  }
+  const bool whole = cfg->index_start == 0 && cfg->index_end == 0;
+  if (!whole && cfg->index_start >= cfg->index_end) {
+    set_error("empty or inverted index range");
+    return POST_ERR_INVALID_ARGS;
+  }
+  return POST_OK;
+}
+
+int post_verify_data_buffer(const uint8_t *labels, uint64_t count,
+                            uint64_t index_base, const uint8_t node_id[32],
+                            const uint8_t commitment_atx_id[32],
+                            uint32_t scrypt_n, const PostAuditConfig *cfg,
+                            PostBadLabel *bad, uint32_t cap,
+                            PostAuditReport *report) {
+  if (!labels || !node_id || !commitment_atx_id || count == 0 ||
+      index_base + count < index_base) {
+    set_error("null or empty label buffer");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (scrypt_n < 2 || (scrypt_n & (scrypt_n - 1))) {
+    set_error("scrypt N must be a power of two >= 2");
+    return POST_ERR_INVALID_ARGS;
+  }
+  int rc = audit_check_args(cfg, bad, cap, report);
+  if (rc != POST_OK) return rc;
+  uint64_t start = index_base, end = index_base + count;
+  if (cfg->index_start || cfg->index_end) {
+    start = cfg->index_start;
+    end = cfg->index_end;
+  }
+  if (start < index_base || end > index_base + count) {
+    set_error("index range beyond the label buffer");
+    return POST_ERR_INVALID_ARGS;
+  }
+  uint8_t commitment[32];
+  poste::commitment(node_id, commitment_atx_id, commitment);
+  AuditGather gather = [labels, index_base](const uint64_t *idx, uint32_t n,
+                                            uint64_t *out_idx,
+                                            uint8_t *out_lab,
+                                            uint32_t *n_out) {
+    for (uint32_t i = 0; i < n; i++) {
+      out_idx[i] = idx[i];
+      std::memcpy(out_lab + (size_t)i * POST_LABEL_SIZE,
+                  labels + (idx[i] - index_base) * POST_LABEL_SIZE,
+                  POST_LABEL_SIZE);
+    }
+    *n_out = n;
+    return POST_OK;
+  };
+  return audit_core(gather, commitment, scrypt_n, start, end, cfg, bad, cap,
+                    report);
+}
+
+int post_verify_data(const char *data_dir, const PostAuditConfig *cfg,
+                     PostBadLabel *bad, uint32_t cap,
+                     PostAuditReport *report) {
+  if (!data_dir) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  int rc = audit_check_args(cfg, bad, cap, report);
+  if (rc != POST_OK) return rc;
+
+  /* identity and geometry come from the dir's own metadata */
+  std::string j;
+  {
+    const std::string path = std::string(data_dir) + "/postdata_metadata.json";
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) {
+      set_error("cannot read " + path);
+      return POST_ERR_IO;
+    }
+    char buf[4096];
+    size_t rd;
+    while ((rd = std::fread(buf, 1, sizeof buf, f)) > 0) j.append(buf, rd);
+    std::fclose(f);
+  }
+  auto lacking = [](const char *field) {
+    set_error(std::string("postdata_metadata.json lacks a valid ") + field);
+    return POST_ERR_IO;
+  };
+  /* strict number reader: the audit is what runs on a damaged dir, so a
+   * key followed by anything but a plain decimal that fits 64 bits counts
+   * as lacking (md_find_u64 would read it as 0 or clamp it) */
+  auto find_u64 = [&j](const char *key, uint64_t &out) {
+    const std::string pat = std::string("\"") + key + "\": ";
+    const size_t p = j.find(pat);
+    if (p == std::string::npos) return false;
+    const char *b = j.c_str() + p + pat.size();
+    if (*b < '0' || *b > '9') return false;
+    char *e = nullptr;
+    errno = 0;
+    out = strtoull(b, &e, 10);
+    return errno == 0 && e != b;
+  };
+  std::string nid_b64, atx_b64;
+  uint8_t node_id[32], atx_id[32];
+  uint64_t lpu = 0, units = 0, max_file = 0, n = 0;
+  if (!md_find_string(j, "NodeId", nid_b64) ||
+      !b64_decode(nid_b64, node_id, 32))
+    return lacking("NodeId");
+  if (!md_find_string(j, "CommitmentAtxId", atx_b64) ||
+      !b64_decode(atx_b64, atx_id, 32))
+    return lacking("CommitmentAtxId");
+  if (!find_u64("LabelsPerUnit", lpu) || lpu == 0)
+    return lacking("LabelsPerUnit");
+  if (!find_u64("NumUnits", units) || units == 0)
+    return lacking("NumUnits");
+  if (!find_u64("MaxFileSize", max_file) || max_file == 0)
+    return lacking("MaxFileSize");
+  if (!find_u64("N", n) || n < 2 || n > (1ull << 31) || (n & (n - 1)))
+    return lacking("N");
+
+  if (units > UINT64_MAX / lpu) {
+    set_error("postdata_metadata.json: NumUnits*LabelsPerUnit overflows");
+    return POST_ERR_IO;
+  }
+  const uint64_t total = units * lpu;
+  uint64_t start = 0, end = total;
+  if (cfg->index_start || cfg->index_end) {
+    start = cfg->index_start;
+    end = cfg->index_end;
+  }
+  if (end > total) {
+    set_error("index range beyond NumUnits*LabelsPerUnit");
+    return POST_ERR_INVALID_ARGS;
+  }
+
+  AuditDirReader reader;
+  reader.dir = data_dir;
+  reader.per_file = std::max<uint64_t>(1, max_file / POST_LABEL_SIZE);
+  reader.chunk = cfg->sample_every <= AUDIT_SEQ_MAX_K ? AUDIT_SEQ_CHUNK
+                                                      : POST_LABEL_SIZE;
+  uint8_t commitment[32];
+  poste::commitment(node_id, atx_id, commitment);
+  AuditGather gather = [&reader](const uint64_t *idx, uint32_t cnt,
+                                 uint64_t *out_idx, uint8_t *out_lab,
+                                 uint32_t *n_out) {
+    uint32_t got = 0;
+    for (uint32_t i = 0; i < cnt; i++) {
+      const int r =
+          reader.fetch(idx[i], out_lab + (size_t)got * POST_LABEL_SIZE);
+      if (r < 0) return POST_ERR_IO;
+      if (r) out_idx[got++] = idx[i];
+    }
+    *n_out = got;
+    return POST_OK;
+  };
+  return audit_core(gather, commitment, (uint32_t)n, start, end, cfg, bad,
+                    cap, report);
 }
 
 /* ------------------------- verification ------------------------- */

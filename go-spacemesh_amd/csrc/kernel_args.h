@@ -33,6 +33,17 @@ struct LabelKernelArgs {
   uint32_t cand_cap;
 };
 
+/* Postdata audit: the prologue and ROMix kernels run on `label` unchanged
+ * (index-list mode, one commitment); the audit tail compares instead of
+ * storing.  `mismatch` holds label.count entries, so it cannot overflow;
+ * *count is zeroed per batch on the stream. */
+struct AuditKernelArgs {
+  LabelKernelArgs label;
+  const uint4 *expected; /* one 16-B on-disk label per task */
+  PostAuditMismatch *mismatch;
+  unsigned int *count;
+};
+
 struct ScanKernelArgs {
   const uint4 *labels;
   uint64_t count;
@@ -62,6 +73,8 @@ struct VerifyPredArgs {
 extern "C" {
 hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
                                      uint32_t blocks, hipStream_t stream);
+hipError_t poste_launch_label_audit(const AuditKernelArgs *args,
+                                    uint32_t blocks, hipStream_t stream);
 hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
                                            uint32_t blocks,
                                            hipStream_t stream);

@@ -588,6 +588,74 @@ post_label_tail_kernel(LabelKernelArgs a) {
   }
 }
 
+/* audit tail (postdata audit, AuditKernelArgs): PBKDF2(P, X, 1, 32) as in
+ * the tail above, then compare with the label read from disk instead of
+ * storing.  No label output and no VRF tracking; a differing label is
+ * appended as {index, recomputed 16 B}.  Each task appends at most once and
+ * the list holds label.count entries, so a slot is always in bounds. */
+__global__ void __launch_bounds__(POSTE_THREADS)
+post_label_audit_tail_kernel(AuditKernelArgs aa) {
+  const LabelKernelArgs &a = aa.label;
+  const unsigned long long lane =
+      (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long group = lane >> 2;
+  const unsigned long long gstride =
+      ((unsigned long long)gridDim.x * blockDim.x) >> 2;
+  const uint32_t sub = (uint32_t)(lane & 3);
+  const uint4 *X = (const uint4 *)a.xbuf;
+
+  for (unsigned long long task = group; task < a.count;
+       task += gstride) {
+    const unsigned long long index = a.indices ? a.indices[task]
+                                               : a.start + task;
+    const uint32_t *cw = a.commit_ids
+                             ? a.commitments + 8ull * a.commit_ids[task]
+                             : a.commitment_le;
+    uint32_t hi[8], ho[8], m[16];
+    hmac_states_for(cw, index, hi, ho);
+    uint32_t Z0[4], Z1[4];
+    {
+      const uint4 *p = X + task * 8ull;
+      uint4 v0 = p[sub], v1 = p[sub + 4];
+      Z0[0] = v0.x; Z0[1] = v0.y; Z0[2] = v0.z; Z0[3] = v0.w;
+      Z1[0] = v1.x; Z1[1] = v1.y; Z1[2] = v1.z; Z1[3] = v1.w;
+    }
+    uint32_t h[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] = hi[i];
+    z_to_msg_be(Z0, m);
+    sha_compress(h, m);
+    z_to_msg_be(Z1, m);
+    sha_compress(h, m);
+    m[0] = 1;
+    m[1] = 0x80000000u;
+#pragma unroll
+    for (int i = 2; i < 15; i++) m[i] = 0;
+    m[15] = (64 + 128 + 4) * 8;
+    sha_compress(h, m);
+    uint32_t lab_be[8];
+    hmac_outer(ho, h, lab_be);
+
+    if (sub == 0) {
+      const uint4 want = aa.expected[task];
+      const uint4 got = make_uint4(__builtin_bswap32(lab_be[0]),
+                                   __builtin_bswap32(lab_be[1]),
+                                   __builtin_bswap32(lab_be[2]),
+                                   __builtin_bswap32(lab_be[3]));
+      if (got.x != want.x || got.y != want.y || got.z != want.z ||
+          got.w != want.w) {
+        const unsigned int slot = atomicAdd(aa.count, 1u);
+        PostAuditMismatch *o = aa.mismatch + slot;
+        o->index = index;
+        o->label[0] = got.x;
+        o->label[1] = got.y;
+        o->label[2] = got.z;
+        o->label[3] = got.w;
+      }
+    }
+  }
+}
+
 /* ------------------------- proving scan kernel ------------------------- */
 /* ScanKernelArgs: see kernel_args.h */
 
@@ -1102,8 +1170,9 @@ int poste_label_romix_lean_ok(uint32_t scrypt_n, uint32_t gap_shift,
          (uint64_t)scrypt_n * scratch_lanes < (1ull << 32);
 }
 
-hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
-                                     uint32_t blocks, hipStream_t stream) {
+/* prologue + ROMix, the part every label pipeline shares */
+static void launch_label_prologue_romix(const LabelKernelArgs *args,
+                                        uint32_t blocks, hipStream_t stream) {
   /* Two labels per quad (a dual-stream form of the lean kernel, spill-free
    * at 58 VGPRs) measured 4% slower than one label per quad and was
    * removed: profiles/r03_kernel_stats.md. */
@@ -1117,7 +1186,21 @@ hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
     hipLaunchKernelGGL(post_label_romix_gap_kernel, dim3(blocks),
                        dim3(POSTE_THREADS), 0, stream, *args);
   }
+}
+
+hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
+                                     uint32_t blocks, hipStream_t stream) {
+  launch_label_prologue_romix(args, blocks, stream);
   hipLaunchKernelGGL(post_label_tail_kernel, dim3(blocks),
+                     dim3(POSTE_THREADS), 0, stream, *args);
+  return hipGetLastError();
+}
+
+/* postdata audit batch: same prologue and ROMix, then the comparing tail */
+hipError_t poste_launch_label_audit(const AuditKernelArgs *args,
+                                    uint32_t blocks, hipStream_t stream) {
+  launch_label_prologue_romix(&args->label, blocks, stream);
+  hipLaunchKernelGGL(post_label_audit_tail_kernel, dim3(blocks),
                      dim3(POSTE_THREADS), 0, stream, *args);
   return hipGetLastError();
 }

@@ -33,4 +33,11 @@ typedef struct {
   uint32_t pad;
 } PostScanHit;
 
+/* one audited label that differs from disk: its index and the recomputed
+ * 16-B label as the four little-endian words of the on-disk byte stream */
+typedef struct {
+  unsigned long long index;
+  uint32_t label[4];
+} PostAuditMismatch;
+
 #endif /* POST_COMMON_H */

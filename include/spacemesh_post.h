@@ -18,6 +18,8 @@
  *     K3 subset (validation.go:206-209) and selected-index
  *     (activation/malfeasance.go:161-169)
  *   - verify_vrf_nonce -> verifying.VerifyVRFNonce (validation.go:277)
+ *   - verify_data -> sampled audit of the labels on disk (upstream postcli
+ *     -verify -fraction)
  *
  * The Go binding a maintainer would write against this header (cgo shim
  * satisfying PostSetupProvider / PostVerifier / PostClient) is shown in
@@ -259,6 +261,86 @@ int post_verify_batch_seeded(const PostProof *proofs,
 /* verifying.VerifyVRFNonce (validation.go:261-286). */
 int post_verify_vrf_nonce(const PostProofMetadata *meta, uint64_t index,
                           uint32_t scrypt_n, uint32_t provider_id);
+
+/* ---------- postdata audit ---------- */
+/* GPU spot-check of on-disk labels: is what is in postdata_*.bin still what
+ * init wrote?  (The role of upstream postcli's -verify -fraction.)  The
+ * index range [index_start, index_end) is cut into consecutive windows of
+ * sample_every labels (the last may be shorter) and exactly one label per
+ * window, picked by a seeded hash, is recomputed on the GPU and compared
+ * with the 16 bytes on disk.  sample_every = 1 checks every label.  The rule
+ * is integer-exact and restated in DESIGN.md 3.4. */
+
+/* Called once per completed batch on the calling thread; a non-zero return
+ * stops the audit with POST_ERR_CANCELLED. */
+typedef int (*PostAuditProgress)(void *user, uint64_t checked,
+                                 uint64_t to_check);
+
+typedef struct {
+  uint32_t provider_id;
+  uint64_t sample_every;   /* window length K >= 1 */
+  uint64_t seed;
+  /* [index_start, index_end) of the global label space; 0,0 means the whole
+   * space (post_verify_data: NumUnits*LabelsPerUnit from metadata;
+   * post_verify_data_buffer: the buffer's span).  A sharded dir is audited
+   * with its shard's range. */
+  uint64_t index_start;
+  uint64_t index_end;
+  /* scratch budget for the ROMix tables, in bytes; 0 = auto, as in
+   * PostInitConfig */
+  uint64_t scratch_bytes;
+  PostAuditProgress progress; /* optional */
+  void *user;                 /* passed back to progress */
+} PostAuditConfig;
+
+typedef struct {
+  uint64_t index;
+  uint8_t on_disk[POST_LABEL_SIZE];
+  uint8_t expected[POST_LABEL_SIZE]; /* recomputed on the GPU */
+} PostBadLabel;
+
+typedef struct {
+  uint64_t labels_in_range; /* index_end - index_start */
+  uint64_t labels_sampled;  /* one per window */
+  uint64_t labels_checked;  /* recomputed and compared */
+  uint64_t labels_missing;  /* sampled, but file absent or too short */
+  uint64_t labels_bad;      /* checked and different; always the full count */
+} PostAuditReport;
+
+/* The sampling rule, host-only (needs no GPU): fills out[0..*n) with the
+ * sampled indices of windows first_window .. first_window + cap - 1 (fewer
+ * at the end of the range) in ascending order. */
+int post_verify_data_sample(uint64_t seed, uint64_t sample_every,
+                            uint64_t index_start, uint64_t index_end,
+                            uint64_t first_window, uint64_t *out,
+                            uint32_t cap, uint32_t *n);
+
+/* Audit a postdata directory.  Identity, LabelsPerUnit, NumUnits,
+ * MaxFileSize and scrypt N come from postdata_metadata.json; label g lives
+ * in postdata_{g / per_file}.bin at byte (g % per_file) * 16 with per_file =
+ * MaxFileSize / 16.  A sampled label whose file is absent or ends before its
+ * 16th byte counts as missing and is not recomputed.
+ *
+ * POST_OK means the audit ran to the end: corruption is reported through
+ * *report, not as an error.  bad[0..min(cap, labels_bad)) receives the
+ * mismatches with the smallest indices, ascending; bad may be NULL when cap
+ * is 0.  Arguments and metadata are validated before a GPU is required:
+ * POST_ERR_INVALID_ARGS (sample_every == 0, empty/inverted range, range
+ * beyond the space), POST_ERR_IO (metadata unreadable or lacking a field),
+ * then POST_ERR_NO_GPU.  POST_ERR_CANCELLED when progress asked to stop.
+ * Audits on different providers may run concurrently in one process. */
+int post_verify_data(const char *data_dir, const PostAuditConfig *cfg,
+                     PostBadLabel *bad, uint32_t cap,
+                     PostAuditReport *report);
+
+/* Same over a host buffer holding labels [index_base, index_base + count)
+ * (bench/tests); 0,0 means that whole span. */
+int post_verify_data_buffer(const uint8_t *labels, uint64_t count,
+                            uint64_t index_base, const uint8_t node_id[32],
+                            const uint8_t commitment_atx_id[32],
+                            uint32_t scrypt_n, const PostAuditConfig *cfg,
+                            PostBadLabel *bad, uint32_t cap,
+                            PostAuditReport *report);
 
 /* ---------- introspection / self-test ---------- */
 /* Engine's independent blake3 (for cross-checking vs the oracle's in

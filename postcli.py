@@ -15,10 +15,16 @@ verification, provider listing and benchmarking
     python postcli.py prove --datadir DIR --challenge HEX32 [--nonces 288]
     python postcli.py verify --datadir DIR --proof proof.json \
         [--k3 K] [--seed HEX]
+    python postcli.py verify-data --datadir DIR [--every K | --fraction PCT] \
+        [--seed S] [--shard R/W | --from I --to J] [--max-report N]
 
 init resumes automatically from existing postdata_*.bin
 (activation/post.go:267-271); --shard R/W initializes only rank R of W
 contiguous index-range shards (the multi-GPU axis).
+
+verify-data audits the labels on disk (upstream postcli -verify -fraction):
+one label per window of K labels is recomputed on the GPU and compared with
+the file bytes; exit status 1 when any sampled label is bad or missing.
 """
 import argparse
 import base64
@@ -159,7 +165,84 @@ def cmd_verify(args):
         sys.exit(1)
 
 
-def main():
+def audit_period(args):
+    """--every K, or --fraction PCT as K = max(1, round(100 / PCT));
+    default --fraction 1."""
+    if args.every is not None:
+        if args.every < 1:
+            raise SystemExit("--every must be >= 1")
+        return args.every
+    pct = 1.0 if args.fraction is None else args.fraction
+    if not 0 < pct <= 100:
+        raise SystemExit("--fraction must be in (0, 100]")
+    return max(1, round(100 / pct))
+
+
+def audit_range(args, total_labels):
+    """[start, end) to audit: --shard R/W, --from/--to, or 0,0 (all)."""
+    if args.shard:
+        if args.index_from is not None or args.index_to is not None:
+            raise SystemExit("--shard excludes --from/--to")
+        import importlib
+        sharding = importlib.import_module("go-spacemesh_amd.sharding")
+        r, w = (int(x) for x in args.shard.split("/"))
+        return sharding.shard_range(total_labels, w, r)
+    if args.index_from is None and args.index_to is None:
+        return 0, 0
+    return (args.index_from or 0,
+            total_labels if args.index_to is None else args.index_to)
+
+
+def cmd_verify_data(args):
+    # the engine reads and checks the dir's metadata itself; the CLI needs
+    # the label count only to turn --shard or an open --from into a range
+    total = 0
+    if args.shard or (args.index_from is not None and args.index_to is None):
+        try:
+            total = wire.PostMetadata.read(args.datadir).num_labels()
+        except (OSError, KeyError, ValueError, TypeError) as e:
+            print(f"verify-data failed: cannot read postdata_metadata.json: "
+                  f"{e!r}", file=sys.stderr)
+            return 2
+    start, end = audit_range(args, total)
+    opts = gsm_amd.AuditOpts(
+        sample_every=audit_period(args), seed=args.seed, index_start=start,
+        index_end=end, provider_id=args.provider, max_report=args.max_report)
+    last = [time.time()]
+
+    def progress(checked, to_check):
+        if time.time() - last[0] >= 5:
+            last[0] = time.time()
+            print(f"  {checked}/{to_check} labels", file=sys.stderr)
+
+    print(f"auditing every {opts.sample_every} labels of "
+          + (f"[{start}, {end})" if end else "the whole label space"),
+          file=sys.stderr)
+    t0 = time.time()
+    try:
+        rep = gsm_amd.verify_data(args.datadir, opts, progress)
+    except gsm_amd.EngineError as e:
+        print(f"verify-data failed: {e}", file=sys.stderr)
+        return 2
+    dt = time.time() - t0
+    print(json.dumps({
+        "sample_every": opts.sample_every, "seed": opts.seed,
+        "index_start": start, "index_end": start + rep.labels_in_range,
+        "labels_in_range": rep.labels_in_range,
+        "labels_sampled": rep.labels_sampled,
+        "labels_checked": rep.labels_checked,
+        "labels_missing": rep.labels_missing,
+        "labels_bad": rep.labels_bad,
+        "bad": [{"index": i, "on_disk": d.hex(), "expected": x.hex()}
+                for i, d, x in rep.bad],
+        "seconds": round(dt, 2),
+        "labels_per_sec": round(rep.labels_checked / dt, 1) if dt > 0
+        else None,
+    }))
+    return 0 if rep.clean else 1
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
     sub.add_parser("providers").set_defaults(fn=cmd_providers)
@@ -194,7 +277,25 @@ def main():
     v.add_argument("--seed", default=None)
     v.add_argument("--pow-difficulty", default=None)
     v.set_defaults(fn=cmd_verify)
-    args = ap.parse_args()
+    a = sub.add_parser("verify-data")
+    a.add_argument("--datadir", required=True)
+    how = a.add_mutually_exclusive_group()
+    how.add_argument("--every", type=int, default=None,
+                     help="check one label per K (1 = every label)")
+    how.add_argument("--fraction", type=float, default=None,
+                     help="percent of labels to check (default 1)")
+    a.add_argument("--seed", type=lambda x: int(x, 0), default=0)
+    a.add_argument("--shard", default=None, help="R/W index-range shard")
+    a.add_argument("--from", dest="index_from", type=int, default=None)
+    a.add_argument("--to", dest="index_to", type=int, default=None)
+    a.add_argument("--provider", type=int, default=0)
+    a.add_argument("--max-report", type=int, default=64)
+    a.set_defaults(fn=cmd_verify_data)
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     sys.exit(args.fn(args))
 
 
