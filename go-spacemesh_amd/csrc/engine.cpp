@@ -286,7 +286,44 @@ struct PostInitSession {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_kernel_ms = 0; /* accumulated over the last post_init_step */
 
+  /* split-kernel init path (init_step_split): 0 = monolithic ROMix on
+   * `stream`; 2 = phase-mixed, the two halves of the slots on `stream` and
+   * `stream_b`; 1 = the split kernels on `stream` alone (measurement).
+   * Buffer set 1 and `copy_stream` double-buffer what the host reads, so
+   * batch i is processed while batch i+1 runs. */
+  int split_streams = 0;
+  uint32_t cand_cap = 0;
+  uint8_t *d_out1 = nullptr;
+  PostVrfCandidate *d_cand1 = nullptr;
+  unsigned int *d_cand_count1 = nullptr;
+  uint8_t *h_batch1 = nullptr;                       /* pinned */
+  PostVrfCandidate *h_cand[2] = {nullptr, nullptr};  /* pinned */
+  unsigned int *h_cand_count = nullptr;              /* pinned, 2 entries */
+  hipStream_t stream_b = nullptr, copy_stream = nullptr;
+  hipEvent_t ev_fill[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_tail[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  hipEvent_t ev_end[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+
   ~PostInitSession() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (stream_b) (void)hipStreamSynchronize(stream_b);
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+    for (int i = 0; i < 4; i++)
+      if (ev_fill[i]) (void)hipEventDestroy(ev_fill[i]);
+    for (int i = 0; i < 2; i++) {
+      for (int k = 0; k < 2; k++)
+        if (ev_tail[i][k]) (void)hipEventDestroy(ev_tail[i][k]);
+      if (ev_end[i]) (void)hipEventDestroy(ev_end[i]);
+      if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
+      if (h_cand[i]) (void)hipHostFree(h_cand[i]);
+    }
+    if (stream_b) (void)hipStreamDestroy(stream_b);
+    if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    if (d_out1) (void)hipFree(d_out1);
+    if (d_cand1) (void)hipFree(d_cand1);
+    if (d_cand_count1) (void)hipFree(d_cand_count1);
+    if (h_batch1) (void)hipHostFree(h_batch1);
+    if (h_cand_count) (void)hipHostFree(h_cand_count);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (stream) (void)hipStreamDestroy(stream);
@@ -407,11 +444,57 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
     HIP_TRY(hipMalloc(&s->d_all, (size_t)keep_bytes));
   }
   HIP_TRY(hipMalloc(&s->d_out, (size_t)s->batch * POST_LABEL_SIZE));
-  HIP_TRY(hipMalloc(&s->d_cand, sizeof(PostVrfCandidate) * CAND_CAP));
-  HIP_TRY(hipMalloc(&s->d_xbuf, (size_t)s->batch * 128));
+  /* The tail appends one candidate per workgroup per launch, whatever the
+   * threshold.  The split path launches one tail per unit of at most
+   * lanes/2 labels, so a batch appends at most batch/64 plus one ragged
+   * workgroup per unit (at most 8 units) — also when the threshold it was
+   * given lags the host's by the batches in flight. */
+  s->cand_cap =
+      (uint32_t)std::max<uint64_t>(CAND_CAP, s->batch / 64 + 16);
+  HIP_TRY(hipMalloc(&s->d_cand, sizeof(PostVrfCandidate) * s->cand_cap));
+  /* at least one unit per stream of the split path: lanes tasks */
+  HIP_TRY(hipMalloc(&s->d_xbuf,
+                    (size_t)std::max<uint64_t>(s->batch, lanes) * 128));
   HIP_TRY(hipMalloc(&s->d_cand_count, sizeof(unsigned int)));
   HIP_TRY(hipHostMalloc(&s->h_batch, (size_t)s->batch * POST_LABEL_SIZE));
   HIP_TRY(hipStreamCreate(&s->stream));
+
+  /* POST_ROMIX_MIX: unset = phase-mixed wherever the lean gap-1 kernel
+   * applies; 0 = the monolithic kernel on one stream (A/B, fallback);
+   * seq = the split kernels back to back on one stream (measures the
+   * phases apart: profiles/r04_romix_phases.md) */
+  {
+    const char *mx = getenv("POST_ROMIX_MIX");
+    const bool lean = poste_label_romix_lean_ok(cfg->scrypt_n, s->gap_shift,
+                                                lanes) != 0;
+    if (!lean || (mx && std::strcmp(mx, "0") == 0))
+      s->split_streams = 0;
+    else if (mx && std::strcmp(mx, "seq") == 0)
+      s->split_streams = 1;
+    else
+      s->split_streams = lanes >= 128 ? 2 : 0;
+  }
+  if (s->split_streams) {
+    if (!s->keep_all)
+      HIP_TRY(hipMalloc(&s->d_out1, (size_t)s->batch * POST_LABEL_SIZE));
+    HIP_TRY(hipMalloc(&s->d_cand1, sizeof(PostVrfCandidate) * s->cand_cap));
+    HIP_TRY(hipMalloc(&s->d_cand_count1, sizeof(unsigned int)));
+    HIP_TRY(hipHostMalloc(&s->h_batch1, (size_t)s->batch * POST_LABEL_SIZE));
+    HIP_TRY(hipHostMalloc(&s->h_cand_count, 2 * sizeof(unsigned int)));
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(hipHostMalloc(&s->h_cand[i],
+                            sizeof(PostVrfCandidate) * s->cand_cap));
+      HIP_TRY(hipEventCreate(&s->ev_end[i]));
+      HIP_TRY(hipEventCreateWithFlags(&s->ev_done[i], hipEventDisableTiming));
+      for (int k = 0; k < 2; k++)
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_tail[i][k],
+                                        hipEventDisableTiming));
+    }
+    for (int i = 0; i < 4; i++)
+      HIP_TRY(hipEventCreateWithFlags(&s->ev_fill[i], hipEventDisableTiming));
+    if (s->split_streams == 2) HIP_TRY(hipStreamCreate(&s->stream_b));
+    HIP_TRY(hipStreamCreate(&s->copy_stream));
+  }
 
   if (!s->data_dir.empty()) {
     /* the dir is bound to one identity/config (verifyMetadata role) */
@@ -637,11 +720,259 @@ static int write_metadata(PostInitSession *s) {
   return POST_OK;
 }
 
+/* Init step on the split ROMix kernels (lean gap-1 geometry only).
+ *
+ * The slots are divided among split_streams streams (two halves when
+ * phase-mixed).  Work is issued in units of at most one half of the slots:
+ * prologue -> fill -> mix -> tail, units alternating between the streams,
+ * and the fill of unit u waits for the fill of unit u-1 on the other
+ * stream.  That holds stream B one phase behind stream A for the whole
+ * call: while one half of the chip's waves streams writes, the other half
+ * random-reads, and the event chain never lets them fall back into step.
+ *
+ * Batches (s->batch labels, as on the monolithic path) only group what the
+ * host reads.  Their outputs are double-buffered and copied by
+ * copy_stream, so the host merges candidates, self-checks and writes batch
+ * i while batch i+1 runs; units are issued across batch boundaries without
+ * a drain.  The pipeline drains at the end of the call, on cancel and on
+ * error.  The threshold a tail is given lags the host's by the batch in
+ * flight; the host merge compares exactly, so the nonce is the same. */
+static int init_step_split(PostInitSession *s, uint64_t max_labels,
+                           uint64_t *done) {
+  const int ns = s->split_streams;
+  const uint64_t unit = s->lanes / (uint64_t)ns; /* slots per unit */
+  hipStream_t st[2] = {s->stream, s->stream_b};
+  uint8_t *const d_outs[2] = {s->d_out, s->d_out1};
+  uint8_t *const h_batches[2] = {s->h_batch, s->h_batch1};
+  PostVrfCandidate *const d_cands[2] = {s->d_cand, s->d_cand1};
+  unsigned int *const d_counts[2] = {s->d_cand_count, s->d_cand_count1};
+
+  auto drain = [&] {
+    for (int k = 0; k < ns; k++) (void)hipStreamSynchronize(st[k]);
+    (void)hipStreamSynchronize(s->copy_stream);
+  };
+#define SPLIT_TRY(expr)                                                        \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) {                                                    \
+      drain();                                                                 \
+      return hip_fail(#expr, _e);                                              \
+    }                                                                          \
+  } while (0)
+
+  LabelKernelArgs args;
+  std::memset(&args, 0, sizeof(args));
+  load_commitment_words(s->commitment, args.commitment_le);
+  args.scrypt_n = s->cfg.scrypt_n;
+  args.gap_shift = s->gap_shift;
+  args.scratch = s->d_scratch;
+  args.scratch_lanes = s->lanes;
+  args.has_difficulty = 1;
+  args.cand_cap = s->cand_cap;
+  RomixPhaseArgs ph;
+  std::memset(&ph, 0, sizeof(ph));
+  ph.scratch = s->d_scratch;
+  ph.scratch_lanes = s->lanes;
+  ph.slot_count = unit;
+  ph.scrypt_n = s->cfg.scrypt_n;
+
+  uint8_t cur_difficulty[32];
+  std::memset(cur_difficulty, 0xff, 32); /* track the global minimum */
+  {
+    std::lock_guard<std::mutex> lk(s->nonce_mu);
+    if (s->nonce_found) std::memcpy(cur_difficulty, s->nonce_label, 32);
+  }
+  const char *sp_env = getenv("POST_SELFCHECK_PERIOD");
+  long selfcheck_period = sp_env ? strtol(sp_env, nullptr, 10) : 1;
+  if (selfcheck_period < 1) selfcheck_period = 1;
+
+  if (!s->ev0) SPLIT_TRY(hipEventCreate(&s->ev0));
+  s->last_kernel_ms = 0;
+
+  struct Batch {
+    uint64_t pos = 0, count = 0;
+    uint32_t max_cand = 0; /* workgroups of this batch's tails */
+    int set = 0;
+    bool live = false;
+  };
+  uint64_t unit_seq = 0; /* units issued in this call */
+  uint64_t batch_no = 0;
+  int last_set = -1;
+
+  /* queue one batch: its units on the compute streams, its copies on
+   * copy_stream behind the last tail of each stream */
+  auto issue = [&](Batch &b) -> int {
+    b.set = (int)(batch_no++ & 1);
+    b.max_cand = 0;
+    uint8_t *out =
+        s->keep_all ? s->d_all + b.pos * POST_LABEL_SIZE : d_outs[b.set];
+    args.cand = d_cands[b.set];
+    args.cand_count = d_counts[b.set];
+    difficulty_to_be_words(cur_difficulty, args.difficulty_be);
+    /* the other stream's first tail of this batch follows its fill, which
+     * waits for this stream's fill: ordered behind the reset */
+    SPLIT_TRY(hipMemsetAsync(d_counts[b.set], 0, sizeof(unsigned int),
+                             st[unit_seq % ns]));
+    bool used[2] = {false, false};
+    for (uint64_t off = 0; off < b.count; off += unit) {
+      const int k = (int)(unit_seq % (uint64_t)ns);
+      const uint64_t c = std::min(unit, b.count - off);
+      const uint32_t blocks = (uint32_t)((c + 63) / 64);
+      args.start = s->range_start + b.pos + off;
+      args.count = c;
+      args.xbuf = s->d_xbuf + (uint64_t)k * unit * 32; /* 128 B per task */
+      args.out = out + off * POST_LABEL_SIZE;
+      ph.xbuf = args.xbuf;
+      ph.slot_base = (uint64_t)k * unit;
+      ph.count = c;
+      if (unit_seq == 0) SPLIT_TRY(hipEventRecord(s->ev0, st[k]));
+      SPLIT_TRY(poste_launch_label_prologue(&args, blocks, st[k]));
+      if (ns == 2 && unit_seq > 0)
+        SPLIT_TRY(hipStreamWaitEvent(st[k], s->ev_fill[(unit_seq - 1) & 3],
+                                     0));
+      SPLIT_TRY(poste_launch_romix_fill(&ph, st[k]));
+      if (ns == 2)
+        SPLIT_TRY(hipEventRecord(s->ev_fill[unit_seq & 3], st[k]));
+      SPLIT_TRY(poste_launch_romix_mix(&ph, st[k]));
+      SPLIT_TRY(poste_launch_label_tail(&args, blocks, st[k]));
+      b.max_cand += blocks;
+      used[k] = true;
+      unit_seq++;
+    }
+    for (int k = 0; k < ns; k++) {
+      if (!used[k]) continue;
+      SPLIT_TRY(hipEventRecord(s->ev_tail[b.set][k], st[k]));
+      SPLIT_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_tail[b.set][k], 0));
+    }
+    SPLIT_TRY(hipEventRecord(s->ev_end[b.set], s->copy_stream));
+    SPLIT_TRY(hipMemcpyAsync(h_batches[b.set], out,
+                             b.count * POST_LABEL_SIZE, hipMemcpyDeviceToHost,
+                             s->copy_stream));
+    SPLIT_TRY(hipMemcpyAsync(s->h_cand_count + b.set, d_counts[b.set],
+                             sizeof(unsigned int), hipMemcpyDeviceToHost,
+                             s->copy_stream));
+    /* every candidate the batch can have appended, so nothing is fetched
+     * later behind the next batch's copies */
+    b.max_cand = std::min(b.max_cand, s->cand_cap);
+    SPLIT_TRY(hipMemcpyAsync(s->h_cand[b.set], d_cands[b.set],
+                             sizeof(PostVrfCandidate) * b.max_cand,
+                             hipMemcpyDeviceToHost, s->copy_stream));
+    SPLIT_TRY(hipEventRecord(s->ev_done[b.set], s->copy_stream));
+    last_set = b.set;
+    b.live = true;
+    return POST_OK;
+  };
+
+  /* host side of one batch, as on the monolithic path */
+  auto process = [&](Batch &b) -> int {
+    b.live = false;
+    const bool do_selfcheck =
+        (s->batch_seq++ % (uint64_t)selfcheck_period) == 0;
+    const uint64_t probe = b.count / 2;
+    uint8_t ref[32];
+    /* the host reference label computes while the device runs */
+    const int ref_rc =
+        do_selfcheck
+            ? poste::host_label(s->commitment, s->range_start + b.pos + probe,
+                                s->cfg.scrypt_n, ref)
+            : 0;
+    SPLIT_TRY(hipEventSynchronize(s->ev_done[b.set]));
+    const unsigned int take = std::min(s->h_cand_count[b.set], b.max_cand);
+    const PostVrfCandidate *cands = s->h_cand[b.set];
+    bool nonce_improved = false;
+    if (take > 0) {
+      std::lock_guard<std::mutex> lk(s->nonce_mu);
+      for (unsigned int i = 0; i < take; i++) {
+        uint8_t lab[32];
+        for (int k = 0; k < 8; k++) {
+          uint32_t w = cands[i].label_be[k];
+          lab[4 * k] = (uint8_t)(w >> 24);
+          lab[4 * k + 1] = (uint8_t)(w >> 16);
+          lab[4 * k + 2] = (uint8_t)(w >> 8);
+          lab[4 * k + 3] = (uint8_t)w;
+        }
+        int c = std::memcmp(lab, cur_difficulty, 32);
+        if (!s->nonce_found || c < 0 ||
+            (c == 0 && cands[i].index < s->nonce_idx)) {
+          s->nonce_found = true;
+          s->nonce_idx = cands[i].index;
+          std::memcpy(s->nonce_label, lab, 32);
+          std::memcpy(cur_difficulty, lab, 32);
+          nonce_improved = true;
+        }
+      }
+    }
+    int rc = POST_OK;
+    /* an improved minimum is persisted at once (see post_init_step) */
+    if (nonce_improved && !s->data_dir.empty()) rc = write_metadata(s);
+    if (rc == POST_OK && ref_rc != 0) {
+      set_error("host reference label failed");
+      rc = POST_ERR;
+    }
+    if (rc == POST_OK && do_selfcheck &&
+        std::memcmp(ref, h_batches[b.set] + probe * POST_LABEL_SIZE,
+                    POST_LABEL_SIZE) != 0) {
+      set_error("reference label mismatch: device labels diverge from the "
+                "host reference (ErrReferenceLabelMismatch)");
+      rc = POST_ERR;
+    }
+    if (rc == POST_OK && !s->data_dir.empty())
+      rc = write_batch_files(s, s->range_start + b.pos, b.count,
+                             h_batches[b.set]);
+    if (rc != POST_OK) {
+      drain();
+      return rc;
+    }
+    s->written.store(b.pos + b.count);
+    *done += b.count;
+    return POST_OK;
+  };
+
+  const uint64_t range = s->range_end - s->range_start;
+  uint64_t pos = s->written.load(); /* relative position (resume) */
+  const uint64_t target = std::min(range, pos + max_labels);
+  Batch inflight[2];
+  int cur = 0;
+  bool cancelled = false;
+  while (pos < target) {
+    if (s->cancel.load()) {
+      cancelled = true;
+      break;
+    }
+    Batch &b = inflight[cur];
+    b.pos = pos;
+    b.count = std::min(s->batch, target - pos);
+    int rc = issue(b);
+    if (rc != POST_OK) return rc;
+    pos += b.count;
+    if (inflight[cur ^ 1].live) {
+      rc = process(inflight[cur ^ 1]);
+      if (rc != POST_OK) return rc;
+    }
+    cur ^= 1;
+  }
+  /* the batch still in flight is complete work: hand it over, cancelled or
+   * not, so `written` covers exactly what reached the sink or the files */
+  if (inflight[cur ^ 1].live) {
+    int rc = process(inflight[cur ^ 1]);
+    if (rc != POST_OK) return rc;
+  }
+  drain();
+  if (last_set >= 0) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, s->ev0, s->ev_end[last_set]);
+    s->last_kernel_ms = ms;
+  }
+#undef SPLIT_TRY
+  return cancelled ? POST_ERR_CANCELLED : POST_OK;
+}
+
 int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
   if (!s || !done) return POST_ERR_INVALID_ARGS;
   *done = 0;
   int rc = require_gpu(s->cfg.provider_id);
   if (rc != POST_OK) return rc;
+  if (s->split_streams) return init_step_split(s, max_labels, done);
 
   LabelKernelArgs args;
   std::memset(&args, 0, sizeof(args));
@@ -658,7 +989,7 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
   args.has_difficulty = 1;
   args.cand = s->d_cand;
   args.cand_count = s->d_cand_count;
-  args.cand_cap = CAND_CAP;
+  args.cand_cap = s->cand_cap;
 
   uint8_t cur_difficulty[32];
   std::memset(cur_difficulty, 0xff, 32); /* track the global minimum */
@@ -668,7 +999,7 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
   }
 
   const uint32_t blocks = (uint32_t)(s->lanes / 64); /* 64 quads/block */
-  std::vector<PostVrfCandidate> cands(CAND_CAP);
+  std::vector<PostVrfCandidate> cands(s->cand_cap);
 
   if (!s->ev0) {
     HIP_TRY(hipEventCreate(&s->ev0));
@@ -718,7 +1049,7 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
     HIP_TRY(hipStreamSynchronize(s->stream));
     bool nonce_improved = false;
     if (n_cand > 0) {
-      unsigned int take = std::min(n_cand, CAND_CAP);
+      unsigned int take = std::min(n_cand, s->cand_cap);
       HIP_TRY(hipMemcpy(cands.data(), s->d_cand,
                         sizeof(PostVrfCandidate) * take,
                         hipMemcpyDeviceToHost));
@@ -803,7 +1134,7 @@ static int nonce_only_batch(PostInitSession *s, uint64_t gstart,
   args.has_difficulty = 1;
   args.cand = s->d_cand;
   args.cand_count = s->d_cand_count;
-  args.cand_cap = CAND_CAP;
+  args.cand_cap = s->cand_cap;
   uint8_t cur[32];
   std::memset(cur, 0xff, 32);
   {
@@ -821,7 +1152,7 @@ static int nonce_only_batch(PostInitSession *s, uint64_t gstart,
   HIP_TRY(hipMemcpy(&n_cand, s->d_cand_count, sizeof(n_cand),
                     hipMemcpyDeviceToHost));
   if (n_cand > 0) {
-    unsigned int take = std::min(n_cand, CAND_CAP);
+    unsigned int take = std::min(n_cand, s->cand_cap);
     std::vector<PostVrfCandidate> cands(take);
     HIP_TRY(hipMemcpy(cands.data(), s->d_cand,
                       sizeof(PostVrfCandidate) * take,

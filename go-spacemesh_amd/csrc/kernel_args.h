@@ -33,6 +33,21 @@ struct LabelKernelArgs {
   uint32_t cand_cap;
 };
 
+/* One phase of the split lean gap-1 ROMix: fill (phase 1, V_j = X, BlockMix)
+ * or mix (phase 2, X ^= V_Integerify(X), BlockMix).  A launch owns the
+ * scratch columns [slot_base, slot_base + slot_count) of a scratch that is
+ * scratch_lanes columns wide; task t < count <= slot_count works in column
+ * slot_base + t and keeps its block in xbuf[t] between the two phases. */
+struct RomixPhaseArgs {
+  uint32_t *scratch;
+  uint32_t *xbuf; /* 8 uint4 per task, quad-z chunk layout */
+  uint64_t scratch_lanes;
+  uint64_t slot_base;
+  uint64_t slot_count;
+  uint64_t count;
+  uint32_t scrypt_n;
+};
+
 /* Postdata audit: the prologue and ROMix kernels run on `label` unchanged
  * (index-list mode, one commitment); the audit tail compares instead of
  * storing.  `mismatch` holds label.count entries, so it cannot overflow;
@@ -73,6 +88,17 @@ struct VerifyPredArgs {
 extern "C" {
 hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
                                      uint32_t blocks, hipStream_t stream);
+/* the label pipeline one kernel at a time (phase-mixed init path): the
+ * prologue and tail as in poste_launch_label_kernel, the lean gap-1 ROMix
+ * as its two phases.  The caller checks poste_label_romix_lean_ok. */
+hipError_t poste_launch_label_prologue(const LabelKernelArgs *args,
+                                       uint32_t blocks, hipStream_t stream);
+hipError_t poste_launch_label_tail(const LabelKernelArgs *args,
+                                   uint32_t blocks, hipStream_t stream);
+hipError_t poste_launch_romix_fill(const RomixPhaseArgs *args,
+                                   hipStream_t stream);
+hipError_t poste_launch_romix_mix(const RomixPhaseArgs *args,
+                                  hipStream_t stream);
 hipError_t poste_launch_label_audit(const AuditKernelArgs *args,
                                     uint32_t blocks, hipStream_t stream);
 hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,

@@ -447,6 +447,73 @@ post_label_romix_kernel(LabelKernelArgs a) {
   }
 }
 
+/* ---- the lean kernel as two launches (RomixPhaseArgs, kernel_args.h) ----
+ * Same loop bodies, V layout and 24-bit addressing as the kernel above, one
+ * task per quad and no loop over rounds: fill must have ended before mix
+ * starts, and the next round's fill may only follow this round's mix, which
+ * stream order provides.  X round-trips through xbuf once more, 256 B per
+ * label.  Two launches on different column ranges can run side by side, one
+ * writing while the other reads (engine.cpp, phase-mixed init). */
+__global__ void __launch_bounds__(POSTE_THREADS, 8)
+post_label_romix_fill_kernel(RomixPhaseArgs a) {
+  const unsigned long long lane =
+      (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long task = lane >> 2;
+  const uint32_t sub = (uint32_t)(lane & 3);
+  if (task >= a.count || task >= a.slot_count) return;
+  const uint32_t n = a.scrypt_n;
+  const uint32_t stride16 = ((uint32_t)a.scratch_lanes * 8u) & POSTE_U24;
+  uint4 *p = (uint4 *)a.scratch + ((a.slot_base + task) * 8ull + sub);
+  uint4 *x = (uint4 *)a.xbuf + task * 8ull;
+
+  uint32_t Z0[4], Z1[4];
+  {
+    uint4 v0 = x[sub], v1 = x[sub + 4];
+    Z0[0] = v0.x; Z0[1] = v0.y; Z0[2] = v0.z; Z0[3] = v0.w;
+    Z1[0] = v1.x; Z1[1] = v1.y; Z1[2] = v1.z; Z1[3] = v1.w;
+  }
+  /* phase 1: V_j = X; X = BlockMix(X) */
+  for (uint32_t j = 0; j < n; j++) {
+    VSTORE(p, make_uint4(Z0[0], Z0[1], Z0[2], Z0[3]));
+    VSTORE(p + 4, make_uint4(Z1[0], Z1[1], Z1[2], Z1[3]));
+    p += stride16;
+    blockmix_z(Z0, Z1);
+  }
+  x[sub] = make_uint4(Z0[0], Z0[1], Z0[2], Z0[3]);
+  x[sub + 4] = make_uint4(Z1[0], Z1[1], Z1[2], Z1[3]);
+}
+
+__global__ void __launch_bounds__(POSTE_THREADS, 8)
+post_label_romix_mix_kernel(RomixPhaseArgs a) {
+  const unsigned long long lane =
+      (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long task = lane >> 2;
+  const uint32_t sub = (uint32_t)(lane & 3);
+  if (task >= a.count || task >= a.slot_count) return;
+  const uint32_t n = a.scrypt_n;
+  const uint32_t mask = (n - 1) & POSTE_U24;
+  const uint32_t stride16 = ((uint32_t)a.scratch_lanes * 8u) & POSTE_U24;
+  const uint4 *const qbase =
+      (const uint4 *)a.scratch + ((a.slot_base + task) * 8ull + sub);
+  uint4 *x = (uint4 *)a.xbuf + task * 8ull;
+
+  uint32_t Z0[4], Z1[4];
+  {
+    uint4 v0 = x[sub], v1 = x[sub + 4];
+    Z0[0] = v0.x; Z0[1] = v0.y; Z0[2] = v0.z; Z0[3] = v0.w;
+    Z1[0] = v1.x; Z1[1] = v1.y; Z1[2] = v1.z; Z1[3] = v1.w;
+  }
+  /* phase 2: j = Integerify(X) & (n-1); X ^= V_j; BlockMix */
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t j = SWZ(Z1[0], QBCAST0) & mask;
+    const uint4 *p = vblock(qbase, j, stride16);
+    const uint4 v0 = VLOAD(p), v1 = VLOAD(p + 4);
+    blockmix_xor_z(Z0, Z1, v0, v1);
+  }
+  x[sub] = make_uint4(Z0[0], Z0[1], Z0[2], Z0[3]);
+  x[sub + 4] = make_uint4(Z1[0], Z1[1], Z1[2], Z1[3]);
+}
+
 /* tail: PBKDF2(P, X, 1, 32) -> labels, VRF-minimum tracking + exact
  * per-workgroup candidate reduce */
 __global__ void __launch_bounds__(POSTE_THREADS)
@@ -1192,6 +1259,48 @@ hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
                                      uint32_t blocks, hipStream_t stream) {
   launch_label_prologue_romix(args, blocks, stream);
   hipLaunchKernelGGL(post_label_tail_kernel, dim3(blocks),
+                     dim3(POSTE_THREADS), 0, stream, *args);
+  return hipGetLastError();
+}
+
+hipError_t poste_launch_label_prologue(const LabelKernelArgs *args,
+                                       uint32_t blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(post_label_prologue_kernel, dim3(blocks),
+                     dim3(POSTE_THREADS), 0, stream, *args);
+  return hipGetLastError();
+}
+
+hipError_t poste_launch_label_tail(const LabelKernelArgs *args,
+                                   uint32_t blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(post_label_tail_kernel, dim3(blocks),
+                     dim3(POSTE_THREADS), 0, stream, *args);
+  return hipGetLastError();
+}
+
+/* a phase launch must stay inside its columns and inside what the lean
+ * addressing reaches; one workgroup per 64 tasks */
+static bool romix_phase_ok(const RomixPhaseArgs *a) {
+  return a->count >= 1 && a->count <= a->slot_count &&
+         a->slot_base + a->slot_count <= a->scratch_lanes &&
+         poste_label_romix_lean_ok(a->scrypt_n, 0, a->scratch_lanes);
+}
+
+hipError_t poste_launch_romix_fill(const RomixPhaseArgs *args,
+                                   hipStream_t stream) {
+  if (!romix_phase_ok(args)) return hipErrorInvalidValue;
+  const uint32_t quads = POSTE_THREADS / 4;
+  hipLaunchKernelGGL(post_label_romix_fill_kernel,
+                     dim3((uint32_t)((args->count + quads - 1) / quads)),
+                     dim3(POSTE_THREADS), 0, stream, *args);
+  return hipGetLastError();
+}
+
+hipError_t poste_launch_romix_mix(const RomixPhaseArgs *args,
+                                  hipStream_t stream) {
+  if (!romix_phase_ok(args)) return hipErrorInvalidValue;
+  const uint32_t quads = POSTE_THREADS / 4;
+  hipLaunchKernelGGL(post_label_romix_mix_kernel,
+                     dim3((uint32_t)((args->count + quads - 1) / quads)),
                      dim3(POSTE_THREADS), 0, stream, *args);
   return hipGetLastError();
 }
