@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """bench_aux.py — auxiliary measurements: the proving scan (BASELINE
-config 4 shape) and batched verification (config 5 shape) on one MI355X.
+config 4 shape), proving over a sealed dir with the seal checked in the same
+pass (against plain proving over that dir), and batched verification
+(config 5 shape) on one MI355X.
 
 Prints one JSON line per measurement.  Run on a GPU box:
     python bench_aux.py [--scan-labels LOG2] [--verify-proofs N]
+(--verify-proofs 0 leaves the verification legs out.)
 
 These are recorded alongside the main bench (profiles/aux_rNN.json); the
 headline metric stays bench.py's labels/s.
@@ -59,6 +62,54 @@ def bench_scan(log2_labels: int):
         "nonce": proof.nonce,
     }))
     return labels, cfg, proof
+
+
+def bench_prove_checked(labels: bytes, cfg, proof, repeats: int = 2):
+    """Proving over a data dir with the seal checked in the same pass
+    (post_prove_checked), against plain post_prove over the same dir.  The
+    dir holds the labels of the scan leg in /dev/shm (memory-backed, so the
+    pass is bound by the pipeline and not by a disk); falls back to the
+    temp dir where there is no /dev/shm."""
+    import shutil
+    import tempfile
+    total = len(labels) // 16
+    per_file = 1 << 22                          # 64 MiB files
+    root = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    d = tempfile.mkdtemp(prefix="post_bench_seal_", dir=root)
+    try:
+        for i in range(-(-total // per_file)):
+            with open(os.path.join(d, f"postdata_{i}.bin"), "wb") as f:
+                f.write(labels[i * per_file * 16:(i + 1) * per_file * 16])
+        t0 = time.perf_counter()
+        gsm_amd.seal_data(d)
+        seal_s = time.perf_counter() - t0
+        opts = gsm_amd.ProveOpts(nonces=288)
+        plain, checked = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            p = gsm_amd.api.prove_dir(d, bytes(32), cfg, opts)
+            plain.append(time.perf_counter() - t0)
+            assert p == proof
+            t0 = time.perf_counter()
+            p, rep = gsm_amd.prove_checked(d, bytes(32), cfg, opts)
+            checked.append(time.perf_counter() - t0)
+            assert p == proof and rep.clean and rep.pages == -(-total // 1024)
+        print(json.dumps({
+            "metric": "prove_checked_labels_per_sec",
+            "value": round(total / min(checked), 1),
+            "unit": "labels/s",
+            "prove_dir_labels_per_sec": round(total / min(plain), 1),
+            "checked_seconds": [round(x, 4) for x in checked],
+            "prove_dir_seconds": [round(x, 4) for x in plain],
+            "seal_seconds": round(seal_s, 3),
+            "config": {"labels": total, "nonces": 288, "k1": 26, "k2": 37,
+                       "dir": "memory-backed" if root else "temp dir",
+                       "seal_stream": os.environ.get("POST_SEAL_STREAM",
+                                                     "second"),
+                       "includes": "k2pow host search + file reads + H2D"},
+        }))
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def bench_verify(n_proofs: int):
@@ -151,8 +202,11 @@ def main():
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs a GPU"
-    bench_scan(args.scan_labels)
-    bench_verify(args.verify_proofs)
+    labels, cfg, proof = bench_scan(args.scan_labels)
+    bench_prove_checked(labels, cfg, proof)
+    del labels
+    if args.verify_proofs > 0:
+        bench_verify(args.verify_proofs)
 
 
 if __name__ == "__main__":

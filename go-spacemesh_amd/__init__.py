@@ -28,9 +28,14 @@ from .api import (  # noqa: F401
     PostSetupOpts,
     PostVerifier,
     ProveOpts,
+    SealReport,
     VerifyOpts,
+    check_seal,
     load_engine,
+    prove_checked,
     sample_indices,
+    seal_data,
+    seal_digest_buffer,
     verify_data,
     verify_data_buffer,
 )
@@ -38,6 +43,7 @@ from .api import (  # noqa: F401
 __all__ = [
     "AuditOpts", "AuditReport", "BatchingVerifier", "Engine", "EngineError", "OffloadingVerifier", "PostConfig", "PostProof",
     "PostProofMetadata", "PostSetupManager", "PostSetupOpts", "PostVerifier",
-    "ProveOpts", "VerifyOpts", "events", "load_engine", "sample_indices",
-    "verify_data", "verify_data_buffer",
+    "ProveOpts", "SealReport", "VerifyOpts", "check_seal", "events",
+    "load_engine", "prove_checked", "sample_indices", "seal_data",
+    "seal_digest_buffer", "verify_data", "verify_data_buffer",
 ]

@@ -116,6 +116,12 @@ class _CAuditReport(ctypes.Structure):
                 ("labels_bad", c_uint64)]
 
 
+class _CSealReport(ctypes.Structure):
+    _fields_ = [("total_labels", c_uint64), ("pages", c_uint64),
+                ("pages_bad", c_uint64),
+                ("proof_touches_bad_page", c_uint32)]
+
+
 _AUDIT_PROGRESS = ctypes.CFUNCTYPE(c_int, c_void_p, c_uint64, c_uint64)
 
 _lib_lock = threading.Lock()
@@ -184,6 +190,17 @@ def load_engine() -> ctypes.CDLL:
                 ctypes.c_char_p, c_uint64, c_uint64, ctypes.c_char_p,
                 ctypes.c_char_p, c_uint32, POINTER(_CAuditConfig),
                 POINTER(_CBadLabel), c_uint32, POINTER(_CAuditReport)]),
+            "post_seal_digest_buffer": (c_int, [
+                ctypes.c_char_p, c_uint64, c_uint32, ctypes.c_char_p,
+                c_uint64, POINTER(c_uint64)]),
+            "post_seal_data": (c_int, [c_char_p, c_uint32,
+                                       POINTER(_CSealReport)]),
+            "post_check_seal": (c_int, [c_char_p, c_uint32,
+                                        POINTER(c_uint64), c_uint32,
+                                        POINTER(_CSealReport)]),
+            "post_prove_checked": (c_int, [
+                c_char_p, POINTER(_CProveConfig), POINTER(CProof),
+                POINTER(c_uint64), c_uint32, POINTER(_CSealReport)]),
             "post_selftest_blake3": (None, [ctypes.c_char_p, c_size_t,
                                             ctypes.c_char_p]),
             "post_selftest_aes128": (None, [ctypes.c_char_p, ctypes.c_char_p,
@@ -514,6 +531,94 @@ def prove_dir(data_dir: str, challenge: bytes, cfg: PostConfig,
     return PostProof(nonce=out.nonce,
                      indices=bytes(out.indices[:out.indices_len]),
                      pow=out.pow)
+
+
+# ------------------------- postdata seal -------------------------
+
+@dataclasses.dataclass
+class SealReport:
+    """Result of seal_data / check_seal / prove_checked."""
+    total_labels: int
+    pages: int
+    pages_bad: int                      # the full count, whatever max_report
+    proof_touches_bad_page: bool = False    # prove_checked only
+    # the max_report smallest bad page numbers, ascending
+    bad_pages: list = dataclasses.field(default_factory=list)
+
+    @property
+    def clean(self) -> bool:
+        return self.pages_bad == 0
+
+    def bad_label_ranges(self) -> list:
+        """[from, to) label ranges of bad_pages, as verify-data takes them."""
+        return [(p * 1024, min((p + 1) * 1024, self.total_labels))
+                for p in self.bad_pages]
+
+
+def _seal_report(rep: _CSealReport, bad, cap: int) -> SealReport:
+    return SealReport(rep.total_labels, rep.pages, rep.pages_bad,
+                      bool(rep.proof_touches_bad_page),
+                      [bad[i] for i in range(min(cap, rep.pages_bad))])
+
+
+def seal_digest_buffer(labels: bytes, provider_id: int = 0) -> bytes:
+    """GPU page digests of a buffer of 16-byte labels, back to back."""
+    eng = Engine()
+    count = len(labels) // LABEL_SIZE
+    cap = -(-count // 1024)
+    out = ctypes.create_string_buffer(max(1, cap * 16))
+    n = c_uint64(0)
+    eng._check(eng.lib.post_seal_digest_buffer(labels, count, provider_id,
+                                               out, cap, byref(n)))
+    return out.raw[:n.value * 16]
+
+
+def seal_data(data_dir: str, provider_id: int = 0) -> SealReport:
+    """Write postdata_seal.bin for the dir's current labels."""
+    eng = Engine()
+    rep = _CSealReport()
+    eng._check(eng.lib.post_seal_data(data_dir.encode(), provider_id,
+                                      byref(rep)))
+    return _seal_report(rep, None, 0)
+
+
+def check_seal(data_dir: str, provider_id: int = 0,
+               max_report: int = 64) -> SealReport:
+    """Compare the dir's labels with its seal.  Corruption is reported
+    through the SealReport, not raised."""
+    eng = Engine()
+    cap = max(0, max_report)
+    bad = (c_uint64 * cap)() if cap else None
+    rep = _CSealReport()
+    eng._check(eng.lib.post_check_seal(data_dir.encode(), provider_id, bad,
+                                       cap, byref(rep)))
+    return _seal_report(rep, bad, cap)
+
+
+def prove_checked(data_dir: str, challenge: bytes, cfg: PostConfig,
+                  opts: ProveOpts, max_report: int = 64) -> tuple:
+    """prove_dir with the seal checked in the same pass: (proof, report).
+    A proof whose report has proof_touches_bad_page set must not be
+    published."""
+    eng = Engine()
+    pc = _CProveConfig()
+    ctypes.memmove(pc.challenge, challenge, 32)
+    pc.k1, pc.k2 = cfg.k1, cfg.k2
+    pc.nonces = opts.nonces
+    ctypes.memmove(pc.pow_difficulty, cfg.pow_difficulty, 32)
+    pc.pow_mode = cfg.pow_mode
+    pc.pow_threads = opts.threads
+    pc.provider_id = opts.provider_id
+    out = CProof()
+    cap = max(0, max_report)
+    bad = (c_uint64 * cap)() if cap else None
+    rep = _CSealReport()
+    eng._check(eng.lib.post_prove_checked(data_dir.encode(), byref(pc),
+                                          byref(out), bad, cap, byref(rep)))
+    proof = PostProof(nonce=out.nonce,
+                      indices=bytes(out.indices[:out.indices_len]),
+                      pow=out.pow)
+    return proof, _seal_report(rep, bad, cap)
 
 
 class PostVerifier:

@@ -1282,8 +1282,168 @@ int post_benchmark(uint32_t provider_id, uint32_t scrypt_n,
 using LabelReader =
     std::function<int(uint64_t base, uint64_t cnt, uint8_t *dst)>;
 
+/* Optional seal step of the pipeline: per chunk, post_seal_kernel hashes the
+ * chunk's pages while it is on the device and `sink` receives the digests of
+ * pages [first_page, first_page + n_pages) on the host, chunk after chunk in
+ * page order.  A non-zero return from sink ends the pass with that status. */
+using SealSink = std::function<int(uint64_t first_page, uint64_t n_pages,
+                                   const uint8_t *digests)>;
+
+constexpr uint64_t SEAL_PAGE = POSTE_SEAL_PAGE_LABELS;
+constexpr uint64_t SEAL_DIGEST = 16;
+
+/* POST_SEAL_STREAM=0 launches the seal step on the scan's own stream instead
+ * of a second one (A/B, profiles/seal.md).  Read per call. */
+static bool seal_on_second_stream() {
+  const char *e = getenv("POST_SEAL_STREAM");
+  return !(e && std::strcmp(e, "0") == 0);
+}
+
+/* The double-buffered read -> pinned -> H2D pipeline of the proving pass:
+ * the disk/host read of chunk i+1 overlaps the device work on chunk i (the
+ * 256-GiB config-4 pass never needs the whole label set in host memory).
+ * Per chunk it launches the scan (`scan` set: te/sbox/rk/difficulty/hits
+ * filled by the caller, labels/count/index_base per chunk here) and/or the
+ * seal step (`seal` set).  With no seal step the queue is what it always
+ * was: H2D, scan, done[parity].
+ *
+ * Seal step: the kernel and the copy of its digests (256 KiB per 2^24-label
+ * chunk) to pinned memory run on a second stream gated by the chunk's H2D
+ * event, beside the scan; the main stream waits for them before it records
+ * done[parity], so the event still means "buffers of this parity are free".
+ * The host hands a chunk's digests to the sink when it comes back to that
+ * parity, and the last two after the drain: always in page order.  Chunks
+ * are a multiple of the page, so no page crosses a chunk. */
+static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
+                          ScanKernelArgs *scan, const SealSink *seal) {
+  uint64_t CHUNK = prove_chunk_labels();
+  if (seal) CHUNK = (CHUNK + SEAL_PAGE - 1) / SEAL_PAGE * SEAL_PAGE;
+  const uint64_t chunk_lab = std::min(CHUNK, num_labels);
+  const uint64_t chunk_pages = (chunk_lab + SEAL_PAGE - 1) / SEAL_PAGE;
+  uint8_t *d_labels[2] = {nullptr, nullptr};
+  uint8_t *h_labels[2] = {nullptr, nullptr};
+  uint8_t *d_dig[2] = {nullptr, nullptr};
+  uint8_t *h_dig[2] = {nullptr, nullptr};
+  hipStream_t stream = nullptr, seal_stream = nullptr;
+  hipEvent_t done[2] = {nullptr, nullptr};
+  hipEvent_t staged[2] = {nullptr, nullptr}, sealed[2] = {nullptr, nullptr};
+  auto cleanup = [&] {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (seal_stream) (void)hipStreamSynchronize(seal_stream);
+    for (int p = 0; p < 2; p++) {
+      if (d_labels[p]) (void)hipFree(d_labels[p]);
+      if (h_labels[p]) (void)hipHostFree(h_labels[p]);
+      if (d_dig[p]) (void)hipFree(d_dig[p]);
+      if (h_dig[p]) (void)hipHostFree(h_dig[p]);
+      if (done[p]) (void)hipEventDestroy(done[p]);
+      if (staged[p]) (void)hipEventDestroy(staged[p]);
+      if (sealed[p]) (void)hipEventDestroy(sealed[p]);
+    }
+    if (stream) (void)hipStreamDestroy(stream);
+    if (seal_stream) (void)hipStreamDestroy(seal_stream);
+  };
+#undef HIP_TRY
+#define HIP_TRY(expr)                                                          \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) {                                                    \
+      cleanup();                                                               \
+      return hip_fail(#expr, _e);                                              \
+    }                                                                          \
+  } while (0)
+  for (int p = 0; p < 2; p++) {
+    HIP_TRY(hipMalloc(&d_labels[p], chunk_lab * 16));
+    HIP_TRY(hipHostMalloc(&h_labels[p], chunk_lab * 16));
+    HIP_TRY(hipEventCreate(&done[p]));
+    if (seal) {
+      HIP_TRY(hipMalloc(&d_dig[p], chunk_pages * SEAL_DIGEST));
+      HIP_TRY(hipHostMalloc(&h_dig[p], chunk_pages * SEAL_DIGEST));
+    }
+  }
+  HIP_TRY(hipStreamCreate(&stream));
+  if (seal && seal_on_second_stream()) {
+    HIP_TRY(hipStreamCreate(&seal_stream));
+    for (int p = 0; p < 2; p++) {
+      HIP_TRY(hipEventCreateWithFlags(&staged[p], hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&sealed[p], hipEventDisableTiming));
+    }
+  }
+
+  /* digests of the chunk in flight on each parity, not yet handed over */
+  uint64_t pend_first[2] = {0, 0}, pend_pages[2] = {0, 0};
+  auto hand_over = [&](int p) -> int {
+    if (!pend_pages[p]) return POST_OK;
+    const uint64_t n = pend_pages[p];
+    pend_pages[p] = 0;
+    return (*seal)(pend_first[p], n, h_dig[p]);
+  };
+
+  int parity = 0;
+  bool inflight[2] = {false, false};
+  for (uint64_t base = 0; base < num_labels; base += CHUNK, parity ^= 1) {
+    uint64_t cnt = std::min(CHUNK, num_labels - base);
+    /* wait until this parity's buffers are free, then stage the chunk */
+    if (inflight[parity]) HIP_TRY(hipEventSynchronize(done[parity]));
+    int rrc = seal ? hand_over(parity) : POST_OK;
+    if (rrc == POST_OK) rrc = read_labels(base, cnt, h_labels[parity]);
+    if (rrc != POST_OK) {
+      cleanup();
+      return rrc;
+    }
+    HIP_TRY(hipMemcpyAsync(d_labels[parity], h_labels[parity], cnt * 16,
+                           hipMemcpyHostToDevice, stream));
+    if (seal_stream) HIP_TRY(hipEventRecord(staged[parity], stream));
+    if (scan) {
+      scan->labels = (const uint4 *)d_labels[parity];
+      scan->count = cnt;
+      scan->index_base = base;
+      uint32_t blocks = (uint32_t)std::min<uint64_t>(
+          (cnt + THREADS - 1) / THREADS, 8192);
+      HIP_TRY(poste_launch_scan_kernel(scan, blocks, stream));
+    }
+    if (seal) {
+      const uint64_t n_pages = (cnt + SEAL_PAGE - 1) / SEAL_PAGE;
+      hipStream_t ss = seal_stream ? seal_stream : stream;
+      SealKernelArgs ka;
+      ka.labels = (const uint4 *)d_labels[parity];
+      ka.count = cnt;
+      ka.digests = (uint4 *)d_dig[parity];
+      if (seal_stream) HIP_TRY(hipStreamWaitEvent(ss, staged[parity], 0));
+      HIP_TRY(poste_launch_seal_kernel(&ka, ss));
+      HIP_TRY(hipMemcpyAsync(h_dig[parity], d_dig[parity],
+                             n_pages * SEAL_DIGEST, hipMemcpyDeviceToHost,
+                             ss));
+      if (seal_stream) {
+        HIP_TRY(hipEventRecord(sealed[parity], ss));
+        HIP_TRY(hipStreamWaitEvent(stream, sealed[parity], 0));
+      }
+      pend_first[parity] = base / SEAL_PAGE;
+      pend_pages[parity] = n_pages;
+    }
+    HIP_TRY(hipEventRecord(done[parity], stream));
+    inflight[parity] = true;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  int rc = POST_OK;
+  if (seal) {
+    /* `parity` now names the older of the two chunks still pending */
+    rc = hand_over(parity);
+    if (rc == POST_OK) rc = hand_over(parity ^ 1);
+  }
+#undef HIP_TRY
+#define HIP_TRY(expr)                                                          \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
+  } while (0)
+  cleanup();
+  return rc;
+}
+
 static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
-                      const PostProveConfig *cfg, PostProof *out) {
+                      const PostProveConfig *cfg, PostProof *out,
+                      const SealSink *seal = nullptr,
+                      std::vector<uint64_t> *winner = nullptr) {
   if (cfg->nonces == 0 || cfg->nonces % POSTE_NONCE_GROUP != 0) {
     set_error("nonces must be a positive multiple of 16");
     return POST_ERR_INVALID_ARGS;
@@ -1318,27 +1478,13 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
   HIP_TRY(hipMalloc(&d_rk, rk.size() * 4));
   HIP_TRY(hipMemcpy(d_rk, rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
 
-  /* double-buffered pipeline: disk/host read of chunk i+1 overlaps the
-   * device scan of chunk i (the 256-GiB config-4 pass never needs the
-   * whole label set in host memory).  Expected total hits = nonces*k1
-   * (a few thousand) regardless of label count, so hits accumulate in one
-   * device buffer drained once at the end. */
-  const uint64_t CHUNK = prove_chunk_labels();
-  const uint64_t chunk_lab = std::min(CHUNK, num_labels);
-  uint8_t *d_labels[2] = {nullptr, nullptr};
-  uint8_t *h_labels[2] = {nullptr, nullptr};
-  hipStream_t stream = nullptr;
-  hipEvent_t done[2] = {nullptr, nullptr};
+  /* Expected total hits = nonces*k1 (a few thousand) regardless of label
+   * count, so hits accumulate in one device buffer drained once at the
+   * end of the pipeline. */
   const uint32_t HIT_CAP = 1u << 22;
   PostScanHit *d_hits = nullptr;
   unsigned int *d_hit_count = nullptr;
   auto cleanup = [&] {
-    for (int p = 0; p < 2; p++) {
-      if (d_labels[p]) (void)hipFree(d_labels[p]);
-      if (h_labels[p]) (void)hipHostFree(h_labels[p]);
-      if (done[p]) (void)hipEventDestroy(done[p]);
-    }
-    if (stream) (void)hipStreamDestroy(stream);
     if (d_hits) (void)hipFree(d_hits);
     if (d_hit_count) (void)hipFree(d_hit_count);
     (void)hipFree(d_rk);
@@ -1352,12 +1498,6 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
       return hip_fail(#expr, _e);                                              \
     }                                                                          \
   } while (0)
-  for (int p = 0; p < 2; p++) {
-    HIP_TRY(hipMalloc(&d_labels[p], chunk_lab * 16));
-    HIP_TRY(hipHostMalloc(&h_labels[p], chunk_lab * 16));
-    HIP_TRY(hipEventCreate(&done[p]));
-  }
-  HIP_TRY(hipStreamCreate(&stream));
   HIP_TRY(hipMalloc(&d_hits, sizeof(PostScanHit) * HIT_CAP));
   HIP_TRY(hipMalloc(&d_hit_count, 4));
   unsigned int zero = 0;
@@ -1374,29 +1514,11 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
   sa.hit_count = d_hit_count;
   sa.hit_cap = HIT_CAP;
 
-  int parity = 0;
-  bool inflight[2] = {false, false};
-  for (uint64_t base = 0; base < num_labels; base += CHUNK, parity ^= 1) {
-    uint64_t cnt = std::min(CHUNK, num_labels - base);
-    /* wait until this parity's buffers are free, then stage the chunk */
-    if (inflight[parity]) HIP_TRY(hipEventSynchronize(done[parity]));
-    int rrc = read_labels(base, cnt, h_labels[parity]);
-    if (rrc != POST_OK) {
-      cleanup();
-      return rrc;
-    }
-    HIP_TRY(hipMemcpyAsync(d_labels[parity], h_labels[parity], cnt * 16,
-                           hipMemcpyHostToDevice, stream));
-    sa.labels = (const uint4 *)d_labels[parity];
-    sa.count = cnt;
-    sa.index_base = base;
-    uint32_t blocks = (uint32_t)std::min<uint64_t>(
-        (cnt + THREADS - 1) / THREADS, 8192);
-    HIP_TRY(poste_launch_scan_kernel(&sa, blocks, stream));
-    HIP_TRY(hipEventRecord(done[parity], stream));
-    inflight[parity] = true;
+  rc = label_pipeline(read_labels, num_labels, &sa, seal);
+  if (rc != POST_OK) {
+    cleanup();
+    return rc;
   }
-  HIP_TRY(hipStreamSynchronize(stream));
   unsigned int n_hits = 0;
   HIP_TRY(hipMemcpy(&n_hits, d_hit_count, 4, hipMemcpyDeviceToHost));
   if (n_hits > HIT_CAP) {
@@ -1448,6 +1570,9 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
     set_error("indices exceed the 800-byte wire cap");
     return POST_ERR;
   }
+  if (winner)
+    winner->assign(per_nonce[best_nonce].begin(),
+                   per_nonce[best_nonce].begin() + cfg->k2);
   return POST_OK;
 }
 
@@ -1578,17 +1703,18 @@ int post_prove_scan(const uint8_t *labels, uint64_t count,
   return POST_OK;
 }
 
-int post_prove(const char *data_dir, const PostProveConfig *cfg,
-               PostProof *out) {
-  if (!data_dir || !cfg || !out) return POST_ERR_INVALID_ARGS;
-  /* map postdata_*.bin in index order; stream chunks (never the whole set
-   * in host memory — config 4 is 256 GiB) */
-  struct FileSpan {
-    std::string path;
-    uint64_t first_label;
-    uint64_t labels;
-  };
-  std::vector<FileSpan> files;
+/* The label stream of a data dir as the proving pass reads it (and as the
+ * seal protects it): postdata_0.bin, postdata_1.bin, ... up to the first
+ * absent file, floor(size / 16) labels of each, concatenated. */
+struct FileSpan {
+  std::string path;
+  uint64_t first_label;
+  uint64_t labels;
+};
+
+/* map postdata_*.bin in index order; returns the stream's label count */
+static uint64_t map_postdata(const char *data_dir,
+                             std::vector<FileSpan> &files) {
   uint64_t total = 0;
   for (uint64_t i = 0;; i++) {
     char path[4096];
@@ -1603,12 +1729,13 @@ int post_prove(const char *data_dir, const PostProveConfig *cfg,
     files.push_back({path, total, nlab});
     total += nlab;
   }
-  if (total == 0) {
-    set_error("no postdata_*.bin in data_dir");
-    return POST_ERR_IO;
-  }
-  LabelReader reader = [&files](uint64_t base, uint64_t cnt, uint8_t *dst)
-      -> int {
+  return total;
+}
+
+/* stream chunks from the mapped files (never the whole set in host memory —
+ * config 4 is 256 GiB); `files` must outlive the reader */
+static LabelReader dir_reader(const std::vector<FileSpan> &files) {
+  return [&files](uint64_t base, uint64_t cnt, uint8_t *dst) -> int {
     uint64_t done = 0;
     for (const auto &fs : files) {
       if (done == cnt) break;
@@ -1637,7 +1764,262 @@ int post_prove(const char *data_dir, const PostProveConfig *cfg,
     }
     return POST_OK;
   };
-  return prove_core(reader, total, cfg, out);
+}
+
+int post_prove(const char *data_dir, const PostProveConfig *cfg,
+               PostProof *out) {
+  if (!data_dir || !cfg || !out) return POST_ERR_INVALID_ARGS;
+  std::vector<FileSpan> files;
+  const uint64_t total = map_postdata(data_dir, files);
+  if (total == 0) {
+    set_error("no postdata_*.bin in data_dir");
+    return POST_ERR_IO;
+  }
+  return prove_core(dir_reader(files), total, cfg, out);
+}
+
+/* ------------------------- postdata seal ------------------------- */
+
+/* postdata_seal.bin: 32-byte little-endian header, then one
+ * 16-byte digest per page of the sealed stream. */
+static const char SEAL_MAGIC[8] = {'P', 'S', 'T', 'S', 'E', 'A', 'L', '1'};
+constexpr uint64_t SEAL_HEADER = 32;
+
+static inline uint64_t seal_pages(uint64_t labels) {
+  return labels / SEAL_PAGE + (labels % SEAL_PAGE ? 1 : 0);
+}
+
+static void put_le(uint8_t *p, uint64_t v, int bytes) {
+  for (int i = 0; i < bytes; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+
+static uint64_t get_le(const uint8_t *p, int bytes) {
+  uint64_t v = 0;
+  for (int i = 0; i < bytes; i++) v |= (uint64_t)p[i] << (8 * i);
+  return v;
+}
+
+/* A sidecar opened for checking against the dir it lies in: every rung of
+ * the validation order of post_check_seal has passed, `f` stands at the
+ * first digest.  Compares what the pipeline hands over page by page. */
+struct SealChecker {
+  FILE *f = nullptr;
+  uint64_t total = 0, pages_bad = 0;
+  uint64_t *bad_pages = nullptr;
+  uint32_t cap = 0;
+  std::vector<bool> *bad_map = nullptr; /* set by prove_checked */
+  std::vector<uint8_t> want;
+
+  ~SealChecker() {
+    if (f) std::fclose(f);
+  }
+
+  int open(const char *data_dir, uint64_t dir_total) {
+    const std::string path = std::string(data_dir) + "/postdata_seal.bin";
+    f = std::fopen(path.c_str(), "rb");
+    if (!f) {
+      set_error("cannot open " + path + " (run seal first)");
+      return POST_ERR_IO;
+    }
+    struct stat st;
+    uint8_t hdr[SEAL_HEADER];
+    const bool have_hdr = fstat(fileno(f), &st) == 0 &&
+                          (uint64_t)st.st_size >= SEAL_HEADER &&
+                          std::fread(hdr, 1, SEAL_HEADER, f) == SEAL_HEADER;
+    const uint64_t hdr_total = have_hdr ? get_le(hdr + 16, 8) : 0;
+    if (!have_hdr || ((uint64_t)st.st_size - SEAL_HEADER) / SEAL_DIGEST <
+                         seal_pages(hdr_total)) {
+      set_error("postdata_seal.bin is shorter than its header and digests");
+      return POST_ERR_IO;
+    }
+    if (std::memcmp(hdr, SEAL_MAGIC, 8) != 0) {
+      set_error("postdata_seal.bin has a wrong magic");
+      return POST_ERR_IO;
+    }
+    if (get_le(hdr + 8, 4) != SEAL_PAGE || get_le(hdr + 12, 4) != SEAL_DIGEST) {
+      set_error("postdata_seal.bin has an unsupported page_labels or "
+                "digest_bytes");
+      return POST_ERR_IO;
+    }
+    if (hdr_total != dir_total) {
+      set_error("postdata length changed since seal");
+      return POST_ERR_IO;
+    }
+    total = hdr_total;
+    return POST_OK;
+  }
+
+  int compare(uint64_t first_page, uint64_t n_pages, const uint8_t *got) {
+    want.resize(n_pages * SEAL_DIGEST);
+    if (std::fread(want.data(), SEAL_DIGEST, n_pages, f) != n_pages) {
+      set_error("short read from postdata_seal.bin");
+      return POST_ERR_IO;
+    }
+    for (uint64_t i = 0; i < n_pages; i++) {
+      if (std::memcmp(want.data() + i * SEAL_DIGEST, got + i * SEAL_DIGEST,
+                      SEAL_DIGEST) == 0)
+        continue;
+      /* pages arrive in ascending order: the first cap are the smallest */
+      if (pages_bad < cap) bad_pages[pages_bad] = first_page + i;
+      if (bad_map) (*bad_map)[first_page + i] = true;
+      pages_bad++;
+    }
+    return POST_OK;
+  }
+
+  void report(PostSealReport *r) const {
+    r->total_labels = total;
+    r->pages = seal_pages(total);
+    r->pages_bad = pages_bad;
+    r->proof_touches_bad_page = 0;
+  }
+};
+
+int post_seal_digest_buffer(const uint8_t *labels, uint64_t count,
+                            uint32_t provider_id, uint8_t *digests,
+                            uint64_t cap_pages, uint64_t *n_pages) {
+  if (!labels || !digests || !n_pages || count == 0) {
+    set_error("null or empty buffer");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (cap_pages < seal_pages(count)) {
+    set_error("digest buffer holds fewer pages than the labels make");
+    return POST_ERR_INVALID_ARGS;
+  }
+  int rc = require_gpu(provider_id);
+  if (rc != POST_OK) return rc;
+  LabelReader reader = [labels](uint64_t base, uint64_t cnt, uint8_t *dst) {
+    std::memcpy(dst, labels + base * 16, cnt * 16);
+    return POST_OK;
+  };
+  SealSink sink = [digests](uint64_t first, uint64_t n, const uint8_t *d) {
+    std::memcpy(digests + first * SEAL_DIGEST, d, n * SEAL_DIGEST);
+    return POST_OK;
+  };
+  rc = label_pipeline(reader, count, nullptr, &sink);
+  if (rc == POST_OK) *n_pages = seal_pages(count);
+  return rc;
+}
+
+int post_seal_data(const char *data_dir, uint32_t provider_id,
+                   PostSealReport *r) {
+  if (!data_dir || !r) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  std::vector<FileSpan> files;
+  const uint64_t total = map_postdata(data_dir, files);
+  if (total == 0) {
+    set_error("no postdata_*.bin in data_dir");
+    return POST_ERR_IO;
+  }
+  int rc = require_gpu(provider_id);
+  if (rc != POST_OK) return rc;
+
+  /* written under a temporary name in the same dir and renamed into place:
+   * a reader sees the old sidecar or the new one, never a part of one */
+  const std::string path = std::string(data_dir) + "/postdata_seal.bin";
+  const std::string tmp = path + ".tmp";
+  FILE *f = std::fopen(tmp.c_str(), "wb");
+  if (!f) {
+    set_error("cannot write " + tmp);
+    return POST_ERR_IO;
+  }
+  uint8_t hdr[SEAL_HEADER] = {0};
+  std::memcpy(hdr, SEAL_MAGIC, 8);
+  put_le(hdr + 8, SEAL_PAGE, 4);
+  put_le(hdr + 12, SEAL_DIGEST, 4);
+  put_le(hdr + 16, total, 8);
+  bool ok = std::fwrite(hdr, 1, SEAL_HEADER, f) == SEAL_HEADER;
+  SealSink sink = [f](uint64_t, uint64_t n, const uint8_t *d) {
+    if (std::fwrite(d, SEAL_DIGEST, n, f) == n) return POST_OK;
+    set_error("short write to postdata_seal.bin.tmp");
+    return POST_ERR_IO;
+  };
+  if (!ok) {
+    set_error("short write to postdata_seal.bin.tmp");
+    rc = POST_ERR_IO;
+  } else {
+    rc = label_pipeline(dir_reader(files), total, nullptr, &sink);
+  }
+  if (rc == POST_OK && (std::fflush(f) != 0 || fsync(fileno(f)) != 0)) {
+    set_error("cannot flush postdata_seal.bin.tmp");
+    rc = POST_ERR_IO;
+  }
+  std::fclose(f);
+  if (rc == POST_OK && std::rename(tmp.c_str(), path.c_str()) != 0) {
+    set_error("cannot rename " + tmp);
+    rc = POST_ERR_IO;
+  }
+  if (rc != POST_OK) {
+    (void)::unlink(tmp.c_str());
+    return rc;
+  }
+  r->total_labels = total;
+  r->pages = seal_pages(total);
+  r->pages_bad = 0;
+  r->proof_touches_bad_page = 0;
+  return POST_OK;
+}
+
+int post_check_seal(const char *data_dir, uint32_t provider_id,
+                    uint64_t *bad_pages, uint32_t cap, PostSealReport *r) {
+  if (!data_dir || !r || (cap > 0 && !bad_pages)) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  std::vector<FileSpan> files;
+  const uint64_t total = map_postdata(data_dir, files);
+  SealChecker chk;
+  int rc = chk.open(data_dir, total);
+  if (rc != POST_OK) return rc;
+  if (total == 0) {
+    set_error("no postdata_*.bin in data_dir");
+    return POST_ERR_IO;
+  }
+  rc = require_gpu(provider_id);
+  if (rc != POST_OK) return rc;
+  chk.bad_pages = bad_pages;
+  chk.cap = cap;
+  SealSink sink = [&chk](uint64_t first, uint64_t n, const uint8_t *d) {
+    return chk.compare(first, n, d);
+  };
+  rc = label_pipeline(dir_reader(files), total, nullptr, &sink);
+  if (rc != POST_OK) return rc;
+  chk.report(r);
+  return POST_OK;
+}
+
+int post_prove_checked(const char *data_dir, const PostProveConfig *cfg,
+                       PostProof *out, uint64_t *bad_pages, uint32_t cap,
+                       PostSealReport *r) {
+  if (!data_dir || !cfg || !out || !r || (cap > 0 && !bad_pages)) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  std::vector<FileSpan> files;
+  const uint64_t total = map_postdata(data_dir, files);
+  SealChecker chk;
+  int rc = chk.open(data_dir, total);
+  if (rc != POST_OK) return rc;
+  if (total == 0) {
+    set_error("no postdata_*.bin in data_dir");
+    return POST_ERR_IO;
+  }
+  std::vector<bool> bad_map(seal_pages(total), false);
+  chk.bad_pages = bad_pages;
+  chk.cap = cap;
+  chk.bad_map = &bad_map;
+  SealSink sink = [&chk](uint64_t first, uint64_t n, const uint8_t *d) {
+    return chk.compare(first, n, d);
+  };
+  std::vector<uint64_t> winner;
+  rc = prove_core(dir_reader(files), total, cfg, out, &sink, &winner);
+  if (rc != POST_OK) return rc;
+  chk.report(r);
+  for (uint64_t idx : winner)
+    if (bad_map[idx / SEAL_PAGE]) r->proof_touches_bad_page = 1;
+  return POST_OK;
 }
 
 /* ------------------------- postdata audit ------------------------- */

@@ -73,6 +73,16 @@ struct ScanKernelArgs {
   uint32_t hit_cap;
 };
 
+/* Postdata seal: page p is labels [1024 p, min(1024 (p + 1), count)) of
+ * `labels`; digests[p] receives the first 16 bytes of SHA-256 over the
+ * page's bytes.  digests holds ceil(count / 1024) entries. */
+#define POSTE_SEAL_PAGE_LABELS 1024
+struct SealKernelArgs {
+  const uint4 *labels;
+  uint64_t count;
+  uint4 *digests;
+};
+
 struct VerifyPredArgs {
   const uint4 *labels2;      /* 2 x uint4 per task (full 32-B labels) */
   uint64_t count;
@@ -106,6 +116,9 @@ hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
                                            hipStream_t stream);
 hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
                                     uint32_t blocks, hipStream_t stream);
+/* one lane per page; hipErrorInvalidValue for an empty or unset buffer */
+hipError_t poste_launch_seal_kernel(const SealKernelArgs *args,
+                                    hipStream_t stream);
 uint64_t poste_label_resident_slots(uint32_t gap_shift);
 /* host-only: does the launcher run the lean gap-1 ROMix kernel here? */
 int poste_label_romix_lean_ok(uint32_t scrypt_n, uint32_t gap_shift,

@@ -15,6 +15,10 @@
  *   n_ciphers ciphers (2 nonces per cipher), T-tables + round keys staged in
  *   LDS, passing (nonce,index) pairs appended with a global atomic.
  *
+ * post_seal_kernel: the postdata seal: 16 bytes of SHA-256 per
+ *   1024-label page of a chunk the proving pass has on the device, one lane
+ *   per page, 64-thread workgroups.
+ *
  * Wave size 64, 256-thread workgroups.  Grid-stride loops size the in-flight
  * label set to the scratch allocation, independent of batch size.
  */
@@ -1218,8 +1222,89 @@ post_verify_pred_kernel(VerifyPredArgs a) {
   }
 }
 
+/* Postdata seal: one lane hashes one 1024-label page of the chunk the
+ * proving pass has already put on the device.  A page of n
+ * labels is n / 4 whole 64-byte blocks and one closing block: the n % 4
+ * labels left over (at most 48 bytes), the 0x80 byte, zeros and the bit
+ * length — 49 bytes at the most before the length, so the padding never
+ * needs a block of its own.  The next block's four loads are issued before
+ * the current block is compressed.  A lane's loads are 64 bytes at a 16 KiB
+ * stride; a whole chunk is only 256 waves, one per CU, which is what lets
+ * the kernel run beside the scan instead of after it. */
+#define POSTE_SEAL_THREADS 64
+
+__global__ void __launch_bounds__(POSTE_SEAL_THREADS)
+post_seal_kernel(SealKernelArgs a) {
+  const unsigned long long pages =
+      (a.count + POSTE_SEAL_PAGE_LABELS - 1) / POSTE_SEAL_PAGE_LABELS;
+  const unsigned long long page =
+      (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (page >= pages) return;
+  const unsigned long long first = page * POSTE_SEAL_PAGE_LABELS;
+  const unsigned long long left = a.count - first;
+  const uint32_t n =
+      left < POSTE_SEAL_PAGE_LABELS ? (uint32_t)left : POSTE_SEAL_PAGE_LABELS;
+  const uint4 *src = a.labels + first;
+  const uint32_t full = n / 4, rest = n % 4;
+
+  uint32_t h[8], m[16];
+  sha_init(h);
+  uint4 q[4];
+  if (full) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) q[i] = src[i];
+  }
+  for (uint32_t b = 0; b < full; b++) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      m[4 * i] = __builtin_bswap32(q[i].x);
+      m[4 * i + 1] = __builtin_bswap32(q[i].y);
+      m[4 * i + 2] = __builtin_bswap32(q[i].z);
+      m[4 * i + 3] = __builtin_bswap32(q[i].w);
+    }
+    if (b + 1 < full) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) q[i] = src[4 * (b + 1) + i];
+    }
+    sha_compress(h, m);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; i++) m[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    if ((uint32_t)i < rest) {
+      const uint4 l = src[4 * full + i];
+      m[4 * i] = __builtin_bswap32(l.x);
+      m[4 * i + 1] = __builtin_bswap32(l.y);
+      m[4 * i + 2] = __builtin_bswap32(l.z);
+      m[4 * i + 3] = __builtin_bswap32(l.w);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    if ((uint32_t)i == rest) m[4 * i] = 0x80000000u;
+  m[15] = n * 128; /* bits; at most 2^17 */
+  sha_compress(h, m);
+  a.digests[page] =
+      make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]),
+                 __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
+}
+
 /* host-visible launchers (called from engine.cpp) */
 extern "C" {
+
+hipError_t poste_launch_seal_kernel(const SealKernelArgs *args,
+                                    hipStream_t stream) {
+  if (!args->labels || !args->digests || args->count == 0)
+    return hipErrorInvalidValue;
+  const uint64_t pages =
+      (args->count + POSTE_SEAL_PAGE_LABELS - 1) / POSTE_SEAL_PAGE_LABELS;
+  hipLaunchKernelGGL(
+      post_seal_kernel,
+      dim3((uint32_t)((pages + POSTE_SEAL_THREADS - 1) / POSTE_SEAL_THREADS)),
+      dim3(POSTE_SEAL_THREADS), 0, stream, *args);
+  return hipGetLastError();
+}
 
 /* Whether the lean gap-1 ROMix kernel can address this scratch geometry:
  * its block offset is a 24-bit x 24-bit multiply of j < scrypt_n by the

@@ -342,6 +342,72 @@ int post_verify_data_buffer(const uint8_t *labels, uint64_t count,
                             PostBadLabel *bad, uint32_t cap,
                             PostAuditReport *report);
 
+/* ---------- postdata seal ---------- */
+/* Page digests checked during the proving pass: every byte the proving scan
+ * reads is hashed while it is on the device and compared with a digest
+ * written once (the seal), so each epoch's pass covers 100 % of the dir at
+ * no extra IO.  The format is fixed in DESIGN.md 3.5:
+ *
+ *   sealed stream  the labels as post_prove reads the dir: postdata_0.bin,
+ *                  postdata_1.bin, ... up to the first absent file,
+ *                  floor(size / 16) labels of each, concatenated
+ *   page p         labels [1024 p, min(1024 (p + 1), total)) of that stream
+ *                  (16 KiB; the last page may be shorter, a page may span
+ *                  two files)
+ *   digest         the first 16 bytes of SHA-256 over the page's bytes
+ *   sidecar        postdata_seal.bin in the data dir: a 32-byte
+ *                  little-endian header {magic "PSTSEAL1", u32 page_labels =
+ *                  1024, u32 digest_bytes = 16, u64 total_labels, u64 0},
+ *                  then ceil(total / 1024) digests
+ *
+ * A bad page number p is what verify-data confirms by recomputation over
+ * labels [1024 p, 1024 (p + 1)).  Sharded dirs are sealed in their own
+ * stream's terms, not in global-index terms. */
+typedef struct {
+  uint64_t total_labels; /* label count of the sealed stream */
+  uint64_t pages;        /* ceil(total_labels / 1024) */
+  uint64_t pages_bad;    /* always the full count */
+  uint32_t proof_touches_bad_page; /* post_prove_checked only */
+} PostSealReport;
+
+/* GPU page digests of a host buffer of count >= 1 labels (tests, building
+ * block): digests[0 .. 16 * *n_pages).  POST_ERR_INVALID_ARGS when
+ * cap_pages is below ceil(count / 1024). */
+int post_seal_digest_buffer(const uint8_t *labels, uint64_t count,
+                            uint32_t provider_id, uint8_t *digests,
+                            uint64_t cap_pages, uint64_t *n_pages);
+
+/* One pass over the dir that writes the sidecar, under a temporary name in
+ * the same dir (postdata_seal.bin.tmp) renamed into place. */
+int post_seal_data(const char *data_dir, uint32_t provider_id,
+                   PostSealReport *r);
+
+/* One pass over the dir, no proof: recompute the digests and compare them
+ * with the sidecar.  POST_OK means the pass ran to the end: corruption is
+ * reported through *r, not as an error.  bad_pages[0..min(cap, pages_bad))
+ * receives the smallest bad page numbers, ascending; bad_pages may be NULL
+ * when cap is 0.  *r is filled on POST_OK only.
+ *
+ * Validated in this order before a GPU is required: POST_ERR_INVALID_ARGS
+ * (NULL pointer, or cap > 0 with bad_pages NULL); then POST_ERR_IO for a
+ * sidecar that is absent, shorter than its header plus the digests its
+ * header announces, of a wrong magic, of a page_labels other than 1024 or
+ * a digest_bytes other than 16, or whose total_labels differs from the
+ * dir's current label count ("postdata length changed since seal":
+ * truncated, removed or grown files); then POST_ERR_NO_GPU. */
+int post_check_seal(const char *data_dir, uint32_t provider_id,
+                    uint64_t *bad_pages, uint32_t cap, PostSealReport *r);
+
+/* post_prove with the seal checked in the same pass: the proof is the one
+ * post_prove returns; *r and bad_pages as for post_check_seal, validated the
+ * same way before cfg is looked at.  r->proof_touches_bad_page is 1 when
+ * any of the proof's K2 indices lies in a bad page: such a proof may fail on
+ * the verifier's side (an invalid index is grounds for a malfeasance proof,
+ * handler_v1.go:228-247) and must not be published. */
+int post_prove_checked(const char *data_dir, const PostProveConfig *cfg,
+                       PostProof *out, uint64_t *bad_pages, uint32_t cap,
+                       PostSealReport *r);
+
 /* ---------- introspection / self-test ---------- */
 /* Engine's independent blake3 (for cross-checking vs the oracle's in
  * tests; not a product entry point). */

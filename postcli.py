@@ -12,11 +12,14 @@ verification, provider listing and benchmarking
     python postcli.py init --datadir DIR --node-id HEX32 --atx-id HEX32 \
         --num-units U [--labels-per-unit L] [--scrypt-n N] \
         [--max-file-size B] [--shard R/W]
-    python postcli.py prove --datadir DIR --challenge HEX32 [--nonces 288]
+    python postcli.py prove --datadir DIR --challenge HEX32 [--nonces 288] \
+        [--check-seal [--max-report N]]
     python postcli.py verify --datadir DIR --proof proof.json \
         [--k3 K] [--seed HEX]
     python postcli.py verify-data --datadir DIR [--every K | --fraction PCT] \
         [--seed S] [--shard R/W | --from I --to J] [--max-report N]
+    python postcli.py seal --datadir DIR
+    python postcli.py check-seal --datadir DIR [--max-report N]
 
 init resumes automatically from existing postdata_*.bin
 (activation/post.go:267-271); --shard R/W initializes only rank R of W
@@ -25,6 +28,13 @@ contiguous index-range shards (the multi-GPU axis).
 verify-data audits the labels on disk (upstream postcli -verify -fraction):
 one label per window of K labels is recomputed on the GPU and compared with
 the file bytes; exit status 1 when any sampled label is bad or missing.
+
+seal writes postdata_seal.bin, one digest per 1024-label page of the dir
+(DESIGN §3.5); check-seal recomputes the digests on the GPU, prints the bad
+pages as label ranges and exits with status 1 when there is one; prove
+--check-seal does the same check during the proving pass itself, prints the
+ranges on stderr as ready verify-data commands, and withholds a proof that
+has an index in a bad page (exit status 1).
 """
 import argparse
 import base64
@@ -129,9 +139,29 @@ def cmd_prove(args):
     if args.pow_difficulty:
         cfg.pow_difficulty = bytes.fromhex(args.pow_difficulty)
     t0 = time.time()
-    proof = gsm_amd.api.prove_dir(args.datadir,
-                                  bytes.fromhex(args.challenge), cfg,
-                                  gsm_amd.ProveOpts(nonces=args.nonces))
+    if args.check_seal:
+        try:
+            proof, rep = gsm_amd.prove_checked(
+                args.datadir, bytes.fromhex(args.challenge), cfg,
+                gsm_amd.ProveOpts(nonces=args.nonces),
+                max_report=args.max_report)
+        except gsm_amd.EngineError as e:
+            print(f"prove failed: {e}", file=sys.stderr)
+            return 2
+        if not rep.clean:
+            print(f"seal: {rep.pages_bad} of {rep.pages} pages differ from "
+                  "postdata_seal.bin; confirm with", file=sys.stderr)
+            for a, b in rep.bad_label_ranges():
+                print(f"  verify-data --datadir {args.datadir} --every 1 "
+                      f"--from {a} --to {b}", file=sys.stderr)
+        if rep.proof_touches_bad_page:
+            print("the proof has an index in a bad page: not printed, do "
+                  "not publish", file=sys.stderr)
+            return 1
+    else:
+        proof = gsm_amd.api.prove_dir(args.datadir,
+                                      bytes.fromhex(args.challenge), cfg,
+                                      gsm_amd.ProveOpts(nonces=args.nonces))
     out = {"nonce": proof.nonce,
            "indices": base64.b64encode(proof.indices).decode(),
            "pow": proof.pow,
@@ -140,6 +170,36 @@ def cmd_prove(args):
            "scale_encoded_postv1": wire.PostV1(
                proof.nonce, proof.indices, proof.pow).encode().hex()}
     print(json.dumps(out))
+
+
+def cmd_seal(args):
+    t0 = time.time()
+    try:
+        rep = gsm_amd.seal_data(args.datadir, args.provider)
+    except gsm_amd.EngineError as e:
+        print(f"seal failed: {e}", file=sys.stderr)
+        return 2
+    print(json.dumps({"total_labels": rep.total_labels, "pages": rep.pages,
+                      "seconds": round(time.time() - t0, 2)}))
+    return 0
+
+
+def cmd_check_seal(args):
+    t0 = time.time()
+    try:
+        rep = gsm_amd.check_seal(args.datadir, args.provider,
+                                 args.max_report)
+    except gsm_amd.EngineError as e:
+        print(f"check-seal failed: {e}", file=sys.stderr)
+        return 2
+    print(json.dumps({
+        "total_labels": rep.total_labels, "pages": rep.pages,
+        "pages_bad": rep.pages_bad,
+        "bad": [{"page": p, "from": a, "to": b} for p, (a, b)
+                in zip(rep.bad_pages, rep.bad_label_ranges())],
+        "seconds": round(time.time() - t0, 2),
+    }))
+    return 0 if rep.clean else 1
 
 
 def cmd_verify(args):
@@ -269,7 +329,19 @@ def build_parser():
     p.add_argument("--challenge", required=True)
     p.add_argument("--nonces", type=int, default=288)
     p.add_argument("--pow-difficulty", default=None)
+    p.add_argument("--check-seal", action="store_true",
+                   help="check postdata_seal.bin in the same pass")
+    p.add_argument("--max-report", type=int, default=64)
     p.set_defaults(fn=cmd_prove)
+    s = sub.add_parser("seal")
+    s.add_argument("--datadir", required=True)
+    s.add_argument("--provider", type=int, default=0)
+    s.set_defaults(fn=cmd_seal)
+    c = sub.add_parser("check-seal")
+    c.add_argument("--datadir", required=True)
+    c.add_argument("--provider", type=int, default=0)
+    c.add_argument("--max-report", type=int, default=64)
+    c.set_defaults(fn=cmd_check_seal)
     v = sub.add_parser("verify")
     v.add_argument("--datadir", required=True)
     v.add_argument("--proof", required=True)
