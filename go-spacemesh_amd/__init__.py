@@ -21,6 +21,8 @@ from .api import (  # noqa: F401
     AuditReport,
     Engine,
     EngineError,
+    HealOpts,
+    HealReport,
     PostConfig,
     PostProof,
     PostProofMetadata,
@@ -33,6 +35,8 @@ from .api import (  # noqa: F401
     check_seal,
     load_engine,
     prove_checked,
+    prove_healed,
+    repair_data,
     sample_indices,
     seal_data,
     seal_digest_buffer,
@@ -41,9 +45,10 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "AuditOpts", "AuditReport", "BatchingVerifier", "Engine", "EngineError", "OffloadingVerifier", "PostConfig", "PostProof",
+    "AuditOpts", "AuditReport", "BatchingVerifier", "Engine", "EngineError", "HealOpts", "HealReport", "OffloadingVerifier", "PostConfig", "PostProof",
     "PostProofMetadata", "PostSetupManager", "PostSetupOpts", "PostVerifier",
     "ProveOpts", "SealReport", "VerifyOpts", "check_seal", "events",
-    "load_engine", "prove_checked", "sample_indices", "seal_data",
+    "load_engine", "prove_checked", "prove_healed", "repair_data",
+    "sample_indices", "seal_data",
     "seal_digest_buffer", "verify_data", "verify_data_buffer",
 ]

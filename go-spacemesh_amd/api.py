@@ -122,6 +122,23 @@ class _CSealReport(ctypes.Structure):
                 ("proof_touches_bad_page", c_uint32)]
 
 
+class _CHealConfig(ctypes.Structure):
+    _fields_ = [("max_pages", c_uint32), ("write_back", c_uint32),
+                ("scratch_bytes", c_uint64)]
+
+
+class _CHealReport(ctypes.Structure):
+    _fields_ = [("total_labels", c_uint64), ("pages", c_uint64),
+                ("pages_bad", c_uint64),
+                ("proof_touches_bad_page", c_uint32),
+                ("heal_skipped", c_uint32), ("pages_healed", c_uint64),
+                ("pages_unconfirmed", c_uint64),
+                ("labels_repaired", c_uint64), ("hits_dropped", c_uint64),
+                ("hits_added", c_uint64), ("pages_written", c_uint64),
+                ("proof_touches_unconfirmed_page", c_uint32),
+                ("reserved", c_uint32)]
+
+
 _AUDIT_PROGRESS = ctypes.CFUNCTYPE(c_int, c_void_p, c_uint64, c_uint64)
 
 _lib_lock = threading.Lock()
@@ -201,6 +218,13 @@ def load_engine() -> ctypes.CDLL:
             "post_prove_checked": (c_int, [
                 c_char_p, POINTER(_CProveConfig), POINTER(CProof),
                 POINTER(c_uint64), c_uint32, POINTER(_CSealReport)]),
+            "post_prove_healed": (c_int, [
+                c_char_p, POINTER(_CProveConfig), POINTER(_CHealConfig),
+                POINTER(CProof), POINTER(c_uint64), c_uint32,
+                POINTER(_CHealReport)]),
+            "post_repair_data": (c_int, [
+                c_char_p, c_uint32, POINTER(_CHealConfig),
+                POINTER(c_uint64), c_uint32, POINTER(_CHealReport)]),
             "post_selftest_blake3": (None, [ctypes.c_char_p, c_size_t,
                                             ctypes.c_char_p]),
             "post_selftest_aes128": (None, [ctypes.c_char_p, ctypes.c_char_p,
@@ -619,6 +643,104 @@ def prove_checked(data_dir: str, challenge: bytes, cfg: PostConfig,
                       indices=bytes(out.indices[:out.indices_len]),
                       pow=out.pow)
     return proof, _seal_report(rep, bad, cap)
+
+
+# ------------------------- self-healing prove -------------------------
+
+@dataclasses.dataclass
+class HealOpts:
+    """Healing of the pages the seal pass finds bad."""
+    max_pages: int = 0                  # 0 = the engine's default, 4096
+    write_back: bool = False            # write confirmed pages to the files
+    scratch_bytes: int = 0
+
+
+@dataclasses.dataclass
+class HealReport(SealReport):
+    """Result of prove_healed / repair_data.  pages_bad and bad_pages are
+    what the pass found on disk."""
+    heal_skipped: bool = False          # more bad pages than max_pages
+    pages_healed: int = 0               # recomputed: confirmed or not
+    pages_unconfirmed: int = 0          # recomputation and seal disagree
+    labels_repaired: int = 0            # disk bytes != recomputation
+    hits_dropped: int = 0
+    hits_added: int = 0
+    pages_written: int = 0
+    proof_touches_unconfirmed_page: bool = False
+
+    @property
+    def publishable(self) -> bool:
+        """The proof stands on labels that are sealed-and-intact or
+        recomputed-and-confirmed."""
+        return not self.heal_skipped \
+            and not self.proof_touches_bad_page \
+            and not self.proof_touches_unconfirmed_page
+
+    @property
+    def repaired(self) -> bool:
+        """A following check_seal would be clean."""
+        return self.pages_written == self.pages_bad
+
+
+def _heal_config(heal: Optional[HealOpts]) -> _CHealConfig:
+    heal = heal or HealOpts()
+    return _CHealConfig(heal.max_pages, 1 if heal.write_back else 0,
+                        heal.scratch_bytes)
+
+
+def _heal_report(rep: _CHealReport, bad, cap: int) -> HealReport:
+    return HealReport(
+        rep.total_labels, rep.pages, rep.pages_bad,
+        bool(rep.proof_touches_bad_page),
+        [bad[i] for i in range(min(cap, rep.pages_bad))],
+        bool(rep.heal_skipped), rep.pages_healed, rep.pages_unconfirmed,
+        rep.labels_repaired, rep.hits_dropped, rep.hits_added,
+        rep.pages_written, bool(rep.proof_touches_unconfirmed_page))
+
+
+def prove_healed(data_dir: str, challenge: bytes, cfg: PostConfig,
+                 opts: ProveOpts, heal: Optional[HealOpts] = None,
+                 max_report: int = 64) -> tuple:
+    """prove_checked that puts right what it finds: bad pages are recomputed
+    on the GPU, their hits replaced, and (heal.write_back) confirmed pages
+    written over the file bytes: (proof, HealReport).  Publish the proof
+    only when report.publishable."""
+    eng = Engine()
+    pc = _CProveConfig()
+    ctypes.memmove(pc.challenge, challenge, 32)
+    pc.k1, pc.k2 = cfg.k1, cfg.k2
+    pc.nonces = opts.nonces
+    ctypes.memmove(pc.pow_difficulty, cfg.pow_difficulty, 32)
+    pc.pow_mode = cfg.pow_mode
+    pc.pow_threads = opts.threads
+    pc.provider_id = opts.provider_id
+    hc = _heal_config(heal)
+    out = CProof()
+    cap = max(0, max_report)
+    bad = (c_uint64 * cap)() if cap else None
+    rep = _CHealReport()
+    eng._check(eng.lib.post_prove_healed(data_dir.encode(), byref(pc),
+                                         byref(hc), byref(out), bad, cap,
+                                         byref(rep)))
+    proof = PostProof(nonce=out.nonce,
+                      indices=bytes(out.indices[:out.indices_len]),
+                      pow=out.pow)
+    return proof, _heal_report(rep, bad, cap)
+
+
+def repair_data(data_dir: str, heal: Optional[HealOpts] = None,
+                provider_id: int = 0, max_report: int = 64) -> HealReport:
+    """The check-seal pass that recomputes the bad pages and writes the
+    confirmed ones back; no proof.  report.repaired says whether a
+    following check_seal would be clean."""
+    eng = Engine()
+    hc = _heal_config(heal)
+    cap = max(0, max_report)
+    bad = (c_uint64 * cap)() if cap else None
+    rep = _CHealReport()
+    eng._check(eng.lib.post_repair_data(data_dir.encode(), provider_id,
+                                        byref(hc), bad, cap, byref(rep)))
+    return _heal_report(rep, bad, cap)
 
 
 class PostVerifier:

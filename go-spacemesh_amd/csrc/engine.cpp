@@ -1440,10 +1440,20 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
   return rc;
 }
 
+/* Optional step of prove_core between "hits copied back" and "winner
+ * chosen" (post_prove_healed): it may rewrite the hit list, and may launch
+ * further scans with the pass's own arguments — tables, round keys,
+ * difficulty and hit buffers are still allocated, the hit buffers free for
+ * reuse. */
+using HitHook =
+    std::function<int(const ScanKernelArgs &scan,
+                      std::vector<PostScanHit> &hits)>;
+
 static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
                       const PostProveConfig *cfg, PostProof *out,
                       const SealSink *seal = nullptr,
-                      std::vector<uint64_t> *winner = nullptr) {
+                      std::vector<uint64_t> *winner = nullptr,
+                      const HitHook *hook = nullptr) {
   if (cfg->nonces == 0 || cfg->nonces % POSTE_NONCE_GROUP != 0) {
     set_error("nonces must be a positive multiple of 16");
     return POST_ERR_INVALID_ARGS;
@@ -1531,6 +1541,13 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
   if (n_hits)
     HIP_TRY(hipMemcpy(all_hits.data(), d_hits, sizeof(PostScanHit) * n_hits,
                       hipMemcpyDeviceToHost));
+  if (hook) {
+    rc = (*hook)(sa, all_hits);
+    if (rc != POST_OK) {
+      cleanup();
+      return rc;
+    }
+  }
 #undef HIP_TRY
 #define HIP_TRY(expr)                                                          \
   do {                                                                         \
@@ -1808,6 +1825,11 @@ struct SealChecker {
   uint64_t *bad_pages = nullptr;
   uint32_t cap = 0;
   std::vector<bool> *bad_map = nullptr; /* set by prove_checked */
+  /* set by the healing entries: the first keep_cap bad pages, whatever cap
+   * is, each with the digest the sidecar holds for it */
+  std::vector<uint64_t> *keep = nullptr;
+  std::vector<uint8_t> *keep_want = nullptr;
+  uint64_t keep_cap = 0;
   std::vector<uint8_t> want;
 
   ~SealChecker() {
@@ -1862,6 +1884,11 @@ struct SealChecker {
       /* pages arrive in ascending order: the first cap are the smallest */
       if (pages_bad < cap) bad_pages[pages_bad] = first_page + i;
       if (bad_map) (*bad_map)[first_page + i] = true;
+      if (keep && keep->size() < keep_cap) {
+        keep->push_back(first_page + i);
+        keep_want->insert(keep_want->end(), want.data() + i * SEAL_DIGEST,
+                          want.data() + (i + 1) * SEAL_DIGEST);
+      }
       pages_bad++;
     }
     return POST_OK;
@@ -2443,17 +2470,16 @@ int post_verify_data_buffer(const uint8_t *labels, uint64_t count,
                     report);
 }
 
-int post_verify_data(const char *data_dir, const PostAuditConfig *cfg,
-                     PostBadLabel *bad, uint32_t cap,
-                     PostAuditReport *report) {
-  if (!data_dir) {
-    set_error("null args");
-    return POST_ERR_INVALID_ARGS;
-  }
-  int rc = audit_check_args(cfg, bad, cap, report);
-  if (rc != POST_OK) return rc;
+/* Identity and geometry of a data dir, from its own postdata_metadata.json
+ * (the audit and the healing paths).  POST_ERR_IO for a file that cannot be
+ * read or lacks a valid field. */
+struct DirMetadata {
+  uint8_t node_id[32], atx_id[32];
+  uint64_t lpu = 0, units = 0, max_file = 0, n = 0;
+  uint64_t total = 0; /* NumUnits * LabelsPerUnit */
+};
 
-  /* identity and geometry come from the dir's own metadata */
+static int read_dir_metadata(const char *data_dir, DirMetadata &md) {
   std::string j;
   {
     const std::string path = std::string(data_dir) + "/postdata_metadata.json";
@@ -2486,28 +2512,46 @@ int post_verify_data(const char *data_dir, const PostAuditConfig *cfg,
     return errno == 0 && e != b;
   };
   std::string nid_b64, atx_b64;
-  uint8_t node_id[32], atx_id[32];
-  uint64_t lpu = 0, units = 0, max_file = 0, n = 0;
   if (!md_find_string(j, "NodeId", nid_b64) ||
-      !b64_decode(nid_b64, node_id, 32))
+      !b64_decode(nid_b64, md.node_id, 32))
     return lacking("NodeId");
   if (!md_find_string(j, "CommitmentAtxId", atx_b64) ||
-      !b64_decode(atx_b64, atx_id, 32))
+      !b64_decode(atx_b64, md.atx_id, 32))
     return lacking("CommitmentAtxId");
-  if (!find_u64("LabelsPerUnit", lpu) || lpu == 0)
+  if (!find_u64("LabelsPerUnit", md.lpu) || md.lpu == 0)
     return lacking("LabelsPerUnit");
-  if (!find_u64("NumUnits", units) || units == 0)
+  if (!find_u64("NumUnits", md.units) || md.units == 0)
     return lacking("NumUnits");
-  if (!find_u64("MaxFileSize", max_file) || max_file == 0)
+  if (!find_u64("MaxFileSize", md.max_file) || md.max_file == 0)
     return lacking("MaxFileSize");
-  if (!find_u64("N", n) || n < 2 || n > (1ull << 31) || (n & (n - 1)))
+  if (!find_u64("N", md.n) || md.n < 2 || md.n > (1ull << 31) ||
+      (md.n & (md.n - 1)))
     return lacking("N");
 
-  if (units > UINT64_MAX / lpu) {
+  if (md.units > UINT64_MAX / md.lpu) {
     set_error("postdata_metadata.json: NumUnits*LabelsPerUnit overflows");
     return POST_ERR_IO;
   }
-  const uint64_t total = units * lpu;
+  md.total = md.units * md.lpu;
+  return POST_OK;
+}
+
+int post_verify_data(const char *data_dir, const PostAuditConfig *cfg,
+                     PostBadLabel *bad, uint32_t cap,
+                     PostAuditReport *report) {
+  if (!data_dir) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  int rc = audit_check_args(cfg, bad, cap, report);
+  if (rc != POST_OK) return rc;
+
+  /* identity and geometry come from the dir's own metadata */
+  DirMetadata md;
+  rc = read_dir_metadata(data_dir, md);
+  if (rc != POST_OK) return rc;
+  const uint8_t *node_id = md.node_id, *atx_id = md.atx_id;
+  const uint64_t total = md.total, max_file = md.max_file, n = md.n;
   uint64_t start = 0, end = total;
   if (cfg->index_start || cfg->index_end) {
     start = cfg->index_start;
@@ -2540,6 +2584,466 @@ int post_verify_data(const char *data_dir, const PostAuditConfig *cfg,
   };
   return audit_core(gather, commitment, (uint32_t)n, start, end, cfg, bad,
                     cap, report);
+}
+
+/* ------------------------- self-healing prove ------------------------- */
+
+/* DESIGN 3.6.  The pages the seal pass found bad are recomputed from the
+ * dir's identity, the recomputation is held against the sidecar digest by
+ * post_seal_kernel (confirmed / unconfirmed), the proving scan is run again
+ * over the recomputed labels alone, and confirmed pages can be written back.
+ * post_prove_healed and post_repair_data share everything but the rescan. */
+
+constexpr uint32_t HEAL_DEFAULT_MAX_PAGES = 4096;
+
+struct HealWork {
+  /* in */
+  const std::vector<FileSpan> *files = nullptr;
+  uint64_t total = 0; /* labels of the stream */
+  DirMetadata md;
+  uint32_t provider_id = 0;
+  uint64_t scratch_bytes = 0;
+  std::vector<uint64_t> pages; /* bad pages, ascending */
+  std::vector<uint8_t> want;   /* their sidecar digests */
+  /* out */
+  uint8_t *d_labels = nullptr; /* compact buffer: page i at label 1024 i */
+  uint64_t count = 0;          /* its labels: (P - 1) 1024 + n_last */
+  std::vector<uint8_t> labels; /* the same on the host */
+  std::vector<bool> confirmed;
+  uint64_t pages_unconfirmed = 0, labels_repaired = 0, pages_written = 0;
+  uint64_t hits_dropped = 0, hits_added = 0;
+  uint64_t lanes = 0;
+  double t_alloc = 0, t_regen = 0, t_digest = 0, t_rescan = 0, t_write = 0;
+
+  ~HealWork() {
+    if (d_labels) (void)hipFree(d_labels);
+  }
+  uint64_t page_labels(size_t i) const {
+    return std::min<uint64_t>(SEAL_PAGE, total - pages[i] * SEAL_PAGE);
+  }
+};
+
+static double heal_tick() {
+  return std::chrono::duration<double>(
+             std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+/* Healing names a label by its place in the stream, so the stream must be in
+ * global-index terms: every file but the last full, nothing past the space
+ * (a sharded dir, or one with a short middle file, is refused). */
+static int heal_check_layout(const std::vector<FileSpan> &files,
+                             uint64_t total, const DirMetadata &md) {
+  const uint64_t per_file = md.max_file / POST_LABEL_SIZE;
+  for (size_t i = 0; i + 1 < files.size(); i++) {
+    if (files[i].labels != per_file) {
+      set_error("healing needs the label stream in global-index terms: " +
+                files[i].path + " does not hold MaxFileSize / 16 labels");
+      return POST_ERR_UNSUPPORTED;
+    }
+  }
+  if (!files.empty() && files.back().labels > per_file) {
+    set_error("healing needs the label stream in global-index terms: " +
+              files.back().path + " holds more than MaxFileSize / 16 labels");
+    return POST_ERR_UNSUPPORTED;
+  }
+  if (total > md.total) {
+    set_error("healing needs the label stream in global-index terms: the "
+              "dir holds more labels than NumUnits*LabelsPerUnit");
+    return POST_ERR_UNSUPPORTED;
+  }
+  return POST_OK;
+}
+
+/* Steps 4 and 5: recompute w.pages into w.d_labels (index-list mode, lanes
+ * and batches sized as audit_core sizes them), digest the buffer as it
+ * stands, compare with the sidecar, count the labels that differ on disk. */
+static int heal_regenerate(HealWork &w) {
+  int rc = require_gpu(w.provider_id);
+  if (rc != POST_OK) return rc;
+  const size_t P = w.pages.size();
+  /* ascending and inside the stream: only the last entry can be the short
+   * last page, so page i of the compact buffer starts at label 1024 i */
+  if (P == 0 || w.pages[P - 1] >= seal_pages(w.total)) {
+    set_error("bad page beyond the stream");
+    return POST_ERR;
+  }
+  for (size_t i = 0; i + 1 < P; i++) {
+    if (w.pages[i] >= w.pages[i + 1]) {
+      set_error("bad page list is not ascending");
+      return POST_ERR;
+    }
+  }
+  const uint64_t count = (uint64_t)(P - 1) * SEAL_PAGE + w.page_labels(P - 1);
+  std::vector<uint64_t> idx((size_t)count);
+  for (uint64_t q = 0; q < count; q++)
+    idx[(size_t)q] = w.pages[(size_t)(q / SEAL_PAGE)] * SEAL_PAGE +
+                     q % SEAL_PAGE;
+
+  const uint32_t scrypt_n = (uint32_t)w.md.n;
+  const uint32_t gap_shift = pick_gap_shift(scrypt_n);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const uint64_t budget = w.scratch_bytes ? w.scratch_bytes
+                                          : (uint64_t)((double)free_b * 0.80);
+  const uint64_t per_lane = ((uint64_t)scrypt_n >> gap_shift) * 128;
+  uint64_t lanes = budget / per_lane;
+  lanes = std::min<uint64_t>(lanes, std::max<uint64_t>(count, 64));
+  lanes = std::min<uint64_t>(lanes, poste_label_resident_slots(gap_shift));
+  lanes = (lanes / 128) * 128;
+  if (lanes == 0) lanes = 128;
+  const uint64_t batch = std::min<uint64_t>(count, lanes * 4);
+  const uint32_t blocks = (uint32_t)(lanes / 64); /* 64 quads/block */
+  w.lanes = lanes;
+
+  uint32_t *d_scratch = nullptr, *d_xbuf = nullptr;
+  uint64_t *d_idx = nullptr;
+  uint8_t *d_dig = nullptr;
+  auto cleanup = [&] {
+    (void)hipDeviceSynchronize();
+    if (d_scratch) (void)hipFree(d_scratch);
+    if (d_xbuf) (void)hipFree(d_xbuf);
+    if (d_idx) (void)hipFree(d_idx);
+    if (d_dig) (void)hipFree(d_dig);
+  };
+#undef HIP_TRY
+#define HIP_TRY(expr)                                                          \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) {                                                    \
+      cleanup();                                                               \
+      return hip_fail(#expr, _e);                                              \
+    }                                                                          \
+  } while (0)
+  double t0 = heal_tick();
+  HIP_TRY(hipMalloc(&d_scratch, (size_t)lanes * per_lane));
+  HIP_TRY(hipMalloc(&d_xbuf, (size_t)batch * 128));
+  HIP_TRY(hipMalloc(&d_idx, (size_t)count * 8));
+  HIP_TRY(hipMalloc(&d_dig, P * SEAL_DIGEST));
+  HIP_TRY(hipMalloc(&w.d_labels, (size_t)count * POST_LABEL_SIZE));
+  w.count = count;
+  HIP_TRY(hipMemcpy(d_idx, idx.data(), (size_t)count * 8,
+                    hipMemcpyHostToDevice));
+  w.t_alloc = heal_tick() - t0;
+
+  t0 = heal_tick();
+  uint8_t commitment[32];
+  poste::commitment(w.md.node_id, w.md.atx_id, commitment);
+  LabelKernelArgs la;
+  std::memset(&la, 0, sizeof(la));
+  load_commitment_words(commitment, la.commitment_le);
+  la.scrypt_n = scrypt_n;
+  la.gap_shift = gap_shift;
+  la.scratch = d_scratch;
+  la.scratch_lanes = lanes;
+  la.xbuf = d_xbuf;
+  /* the batches share scratch and xbuf: back to back on one stream */
+  for (uint64_t off = 0; off < count; off += batch) {
+    la.count = std::min(batch, count - off);
+    la.indices = d_idx + off;
+    la.out = w.d_labels + off * POST_LABEL_SIZE;
+    HIP_TRY(poste_launch_label_kernel(&la, blocks, nullptr));
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  w.t_regen = heal_tick() - t0;
+
+  t0 = heal_tick();
+  SealKernelArgs ka;
+  ka.labels = (const uint4 *)w.d_labels;
+  ka.count = count;
+  ka.digests = (uint4 *)d_dig;
+  std::vector<uint8_t> got(P * SEAL_DIGEST);
+  HIP_TRY(poste_launch_seal_kernel(&ka, nullptr));
+  HIP_TRY(hipMemcpy(got.data(), d_dig, got.size(), hipMemcpyDeviceToHost));
+  w.t_digest = heal_tick() - t0;
+  w.labels.resize((size_t)count * POST_LABEL_SIZE);
+  HIP_TRY(hipMemcpy(w.labels.data(), w.d_labels, w.labels.size(),
+                    hipMemcpyDeviceToHost));
+#undef HIP_TRY
+#define HIP_TRY(expr)                                                          \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
+  } while (0)
+  cleanup();
+
+  w.confirmed.assign(P, false);
+  const LabelReader read = dir_reader(*w.files);
+  std::vector<uint8_t> disk(SEAL_PAGE * POST_LABEL_SIZE);
+  for (size_t i = 0; i < P; i++) {
+    w.confirmed[i] = std::memcmp(got.data() + i * SEAL_DIGEST,
+                                 w.want.data() + i * SEAL_DIGEST,
+                                 SEAL_DIGEST) == 0;
+    if (!w.confirmed[i]) w.pages_unconfirmed++;
+    const uint64_t n = w.page_labels(i);
+    rc = read(w.pages[i] * SEAL_PAGE, n, disk.data());
+    if (rc != POST_OK) return rc;
+    const uint8_t *fresh = w.labels.data() + i * SEAL_PAGE * POST_LABEL_SIZE;
+    for (uint64_t k = 0; k < n; k++)
+      if (std::memcmp(disk.data() + k * POST_LABEL_SIZE,
+                      fresh + k * POST_LABEL_SIZE, POST_LABEL_SIZE) != 0)
+        w.labels_repaired++;
+  }
+  return POST_OK;
+}
+
+/* Step 6: the production scan over the compact buffer at index base 0, with
+ * the pass's own scan arguments; first-pass hits of bad pages go, the new
+ * ones come in under their global indices. */
+static int heal_rescan(HealWork &w, const ScanKernelArgs &pass,
+                       const std::vector<bool> &bad_map,
+                       std::vector<PostScanHit> &hits) {
+  const double t0 = heal_tick();
+  ScanKernelArgs sa = pass;
+  sa.labels = (const uint4 *)w.d_labels;
+  sa.count = w.count;
+  sa.index_base = 0;
+  HIP_TRY(hipMemset(sa.hit_count, 0, 4));
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>(
+      (w.count + THREADS - 1) / THREADS, 8192);
+  HIP_TRY(poste_launch_scan_kernel(&sa, blocks, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned int got = 0;
+  HIP_TRY(hipMemcpy(&got, sa.hit_count, 4, hipMemcpyDeviceToHost));
+  if (got > sa.hit_cap) {
+    set_error("scan hit buffer overflow (pathological K1/num_labels "
+              "configuration)");
+    return POST_ERR;
+  }
+  std::vector<PostScanHit> fresh(got);
+  if (got)
+    HIP_TRY(hipMemcpy(fresh.data(), sa.hits, sizeof(PostScanHit) * got,
+                      hipMemcpyDeviceToHost));
+  const size_t before = hits.size();
+  hits.erase(std::remove_if(hits.begin(), hits.end(),
+                            [&](const PostScanHit &h) {
+                              return (bool)bad_map[h.index / SEAL_PAGE];
+                            }),
+             hits.end());
+  w.hits_dropped = before - hits.size();
+  for (PostScanHit &h : fresh) {
+    const uint64_t q = h.index;
+    if (q >= w.count) {
+      set_error("rescan hit outside the compact buffer");
+      return POST_ERR;
+    }
+    h.index = w.pages[(size_t)(q / SEAL_PAGE)] * SEAL_PAGE + q % SEAL_PAGE;
+    hits.push_back(h);
+  }
+  w.hits_added = got;
+  w.t_rescan = heal_tick() - t0;
+  return POST_OK;
+}
+
+/* Step 7: confirmed pages over the file bytes; a page may span two files,
+ * every touched file is synced once.  Unconfirmed pages are never written. */
+static int heal_write_back(HealWork &w) {
+  const double t0 = heal_tick();
+  std::map<size_t, int> fds; /* file number -> descriptor */
+  auto close_all = [&] {
+    for (auto &kv : fds) ::close(kv.second);
+  };
+  for (size_t i = 0; i < w.pages.size(); i++) {
+    if (!w.confirmed[i]) continue;
+    uint64_t pos = w.pages[i] * SEAL_PAGE; /* stream label */
+    uint64_t left = w.page_labels(i);
+    const uint8_t *src = w.labels.data() + i * SEAL_PAGE * POST_LABEL_SIZE;
+    for (size_t f = 0; f < w.files->size() && left; f++) {
+      const FileSpan &fs = (*w.files)[f];
+      if (pos < fs.first_label || pos >= fs.first_label + fs.labels) continue;
+      const uint64_t in_file = pos - fs.first_label;
+      const uint64_t take = std::min(fs.labels - in_file, left);
+      auto it = fds.find(f);
+      if (it == fds.end()) {
+        const int fd = ::open(fs.path.c_str(), O_WRONLY);
+        if (fd < 0) {
+          close_all();
+          set_error("cannot open " + fs.path + " for writing");
+          return POST_ERR_IO;
+        }
+        it = fds.emplace(f, fd).first;
+      }
+      size_t done = 0;
+      const size_t bytes = (size_t)take * POST_LABEL_SIZE;
+      while (done < bytes) {
+        const ssize_t r =
+            ::pwrite(it->second, src + done, bytes - done,
+                     (off_t)(in_file * POST_LABEL_SIZE + done));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          close_all();
+          set_error("short write to " + fs.path);
+          return POST_ERR_IO;
+        }
+        done += (size_t)r;
+      }
+      src += bytes;
+      pos += take;
+      left -= take;
+    }
+    if (left) {
+      close_all();
+      set_error("label range not covered by postdata files");
+      return POST_ERR_IO;
+    }
+    w.pages_written++;
+  }
+  int rc = POST_OK;
+  for (auto &kv : fds) {
+    if (::fsync(kv.second) != 0 && rc == POST_OK) {
+      set_error("cannot sync " + (*w.files)[kv.first].path);
+      rc = POST_ERR_IO;
+    }
+  }
+  close_all();
+  w.t_write = heal_tick() - t0;
+  return rc;
+}
+
+static void heal_debug(const HealWork &w) {
+  if (!getenv("POST_HEAL_DEBUG")) return; /* where the time went (stderr) */
+  std::fprintf(stderr,
+               "[heal] pages=%zu labels=%llu lanes=%llu alloc %.4fs "
+               "regenerate %.4fs digest %.4fs rescan %.4fs write %.4fs\n",
+               w.pages.size(), (unsigned long long)w.count,
+               (unsigned long long)w.lanes, w.t_alloc, w.t_regen, w.t_digest,
+               w.t_rescan, w.t_write);
+}
+
+static void heal_report(const SealChecker &chk, const HealWork &w,
+                        bool healed, PostHealReport *r) {
+  std::memset(r, 0, sizeof(*r));
+  r->total_labels = chk.total;
+  r->pages = seal_pages(chk.total);
+  r->pages_bad = chk.pages_bad;
+  if (!healed) return;
+  r->pages_healed = w.pages.size();
+  r->pages_unconfirmed = w.pages_unconfirmed;
+  r->labels_repaired = w.labels_repaired;
+  r->hits_dropped = w.hits_dropped;
+  r->hits_added = w.hits_added;
+  r->pages_written = w.pages_written;
+}
+
+/* the rungs both healing entries share, after their NULL checks and before
+ * a GPU is required */
+static int heal_open(const char *data_dir, std::vector<FileSpan> &files,
+                     SealChecker &chk, HealWork &w) {
+  const uint64_t total = map_postdata(data_dir, files);
+  int rc = chk.open(data_dir, total);
+  if (rc != POST_OK) return rc;
+  if (total == 0) {
+    set_error("no postdata_*.bin in data_dir");
+    return POST_ERR_IO;
+  }
+  rc = read_dir_metadata(data_dir, w.md);
+  if (rc != POST_OK) return rc;
+  rc = heal_check_layout(files, total, w.md);
+  if (rc != POST_OK) return rc;
+  w.files = &files;
+  w.total = total;
+  return POST_OK;
+}
+
+int post_prove_healed(const char *data_dir, const PostProveConfig *cfg,
+                      const PostHealConfig *heal, PostProof *out,
+                      uint64_t *bad_pages, uint32_t cap, PostHealReport *r) {
+  if (!data_dir || !cfg || !heal || !out || !r || (cap > 0 && !bad_pages)) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  std::vector<FileSpan> files;
+  SealChecker chk;
+  HealWork w;
+  int rc = heal_open(data_dir, files, chk, w);
+  if (rc != POST_OK) return rc;
+  const uint64_t limit =
+      heal->max_pages ? heal->max_pages : HEAL_DEFAULT_MAX_PAGES;
+  w.provider_id = cfg->provider_id;
+  w.scratch_bytes = heal->scratch_bytes;
+
+  std::vector<bool> bad_map(seal_pages(w.total), false);
+  chk.bad_pages = bad_pages;
+  chk.cap = cap;
+  chk.bad_map = &bad_map;
+  chk.keep = &w.pages;
+  chk.keep_want = &w.want;
+  chk.keep_cap = limit;
+  SealSink sink = [&chk](uint64_t first, uint64_t n, const uint8_t *d) {
+    return chk.compare(first, n, d);
+  };
+  bool healed = false;
+  /* by the time the hook runs the pass is over: chk holds every bad page */
+  HitHook hook = [&](const ScanKernelArgs &scan,
+                     std::vector<PostScanHit> &hits) -> int {
+    if (chk.pages_bad == 0 || chk.pages_bad > limit) return POST_OK;
+    int hrc = heal_regenerate(w);
+    if (hrc == POST_OK) hrc = heal_rescan(w, scan, bad_map, hits);
+    if (hrc == POST_OK && heal->write_back) hrc = heal_write_back(w);
+    if (hrc == POST_OK) healed = true;
+    return hrc;
+  };
+  std::vector<uint64_t> winner;
+  rc = prove_core(dir_reader(files), w.total, cfg, out, &sink, &winner, &hook);
+  if (healed) heal_debug(w);
+  if (rc != POST_OK) return rc;
+  heal_report(chk, w, healed, r);
+  if (healed) {
+    /* no index of the proof lies in a page that is still bad; what is left
+     * to doubt is a page the seal could not confirm */
+    for (uint64_t idx : winner) {
+      const auto at = std::lower_bound(w.pages.begin(), w.pages.end(),
+                                       idx / SEAL_PAGE);
+      if (at != w.pages.end() && *at == idx / SEAL_PAGE &&
+          !w.confirmed[(size_t)(at - w.pages.begin())])
+        r->proof_touches_unconfirmed_page = 1;
+    }
+  } else if (chk.pages_bad) {
+    r->heal_skipped = 1;
+    for (uint64_t idx : winner)
+      if (bad_map[idx / SEAL_PAGE]) r->proof_touches_bad_page = 1;
+  }
+  return POST_OK;
+}
+
+int post_repair_data(const char *data_dir, uint32_t provider_id,
+                     const PostHealConfig *heal, uint64_t *bad_pages,
+                     uint32_t cap, PostHealReport *r) {
+  if (!data_dir || !heal || !r || (cap > 0 && !bad_pages)) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  std::vector<FileSpan> files;
+  SealChecker chk;
+  HealWork w;
+  int rc = heal_open(data_dir, files, chk, w);
+  if (rc != POST_OK) return rc;
+  rc = require_gpu(provider_id);
+  if (rc != POST_OK) return rc;
+  const uint64_t limit =
+      heal->max_pages ? heal->max_pages : HEAL_DEFAULT_MAX_PAGES;
+  w.provider_id = provider_id;
+  w.scratch_bytes = heal->scratch_bytes;
+  chk.bad_pages = bad_pages;
+  chk.cap = cap;
+  chk.keep = &w.pages;
+  chk.keep_want = &w.want;
+  chk.keep_cap = limit;
+  SealSink sink = [&chk](uint64_t first, uint64_t n, const uint8_t *d) {
+    return chk.compare(first, n, d);
+  };
+  rc = label_pipeline(dir_reader(files), w.total, nullptr, &sink);
+  if (rc != POST_OK) return rc;
+  const bool heal_it = chk.pages_bad && chk.pages_bad <= limit;
+  if (heal_it) {
+    rc = heal_regenerate(w);
+    if (rc == POST_OK) rc = heal_write_back(w);
+    heal_debug(w);
+    if (rc != POST_OK) return rc;
+  }
+  heal_report(chk, w, heal_it, r);
+  if (chk.pages_bad && !heal_it) r->heal_skipped = 1;
+  return POST_OK;
 }
 
 /* ------------------------- verification ------------------------- */

@@ -408,6 +408,76 @@ int post_prove_checked(const char *data_dir, const PostProveConfig *cfg,
                        PostProof *out, uint64_t *bad_pages, uint32_t cap,
                        PostSealReport *r);
 
+/* ---------- self-healing prove ---------- */
+/* What the seal pass finds bad is put right in the same call (DESIGN.md
+ * 3.6): the bad pages are recomputed on the GPU from the identity in
+ * postdata_metadata.json, the proving scan is run again over the recomputed
+ * labels alone, the first pass's hits in bad pages are replaced by the new
+ * ones, and the winner is chosen by the unchanged rule.  The proof is the
+ * one post_prove returns on the undamaged dir.
+ *
+ * A recomputed page whose digest equals the sidecar's is confirmed:
+ * recomputation and seal agree.  One whose digest differs is unconfirmed:
+ * the sidecar entry is wrong, or the seal was taken over data that was
+ * already bad.  The recomputed labels are used either way (they are what a
+ * verifier recomputes); only confirmed pages are ever written back. */
+typedef struct {
+  /* heal at most this many pages; 0 = 4096: 2^22 labels, measured at 2.0 s
+   * of recompute at mainnet N on one MI355X, plus up to a few seconds for
+   * the ROMix scratch (profiles/heal.md).  With more bad pages nothing is
+   * healed and the call is post_prove_checked. */
+  uint32_t max_pages;
+  /* non-zero: pwrite every confirmed page over the file bytes, then fsync
+   * each touched file once (post_repair_data always writes) */
+  uint32_t write_back;
+  /* scratch budget for the ROMix tables, as in PostAuditConfig */
+  uint64_t scratch_bytes;
+} PostHealConfig;
+
+typedef struct {
+  uint64_t total_labels;
+  uint64_t pages;
+  uint64_t pages_bad;              /* as found on disk by the pass */
+  /* only after a skipped heal, then as post_prove_checked sets it: a healed
+   * proof has no index in a page that is still bad */
+  uint32_t proof_touches_bad_page;
+  uint32_t heal_skipped;           /* 1: pages_bad > the limit */
+  uint64_t pages_healed;           /* recomputed and used: confirmed or not */
+  uint64_t pages_unconfirmed;
+  uint64_t labels_repaired;        /* disk bytes != recomputation */
+  uint64_t hits_dropped;           /* first-pass hits in bad pages */
+  uint64_t hits_added;             /* hits of the recomputed labels */
+  uint64_t pages_written;          /* confirmed pages written back */
+  /* any of the proof's K2 indices lies in an unconfirmed page: the proof
+   * stands on labels the seal could not vouch for; do not publish */
+  uint32_t proof_touches_unconfirmed_page;
+  uint32_t reserved;
+} PostHealReport;
+
+/* post_prove_checked that heals.  bad_pages / cap as for post_check_seal
+ * (what the pass found on disk).  POST_OK means the call ran to the end;
+ * *r is filled on POST_OK only.  Pages are written back before the winner
+ * is chosen, so POST_ERR_NO_NONCE can leave a repaired dir behind.
+ *
+ * Validated in this order before a GPU is required: the rungs of
+ * post_check_seal; POST_ERR_IO for a postdata_metadata.json that cannot be
+ * read or lacks a field (as post_verify_data); POST_ERR_UNSUPPORTED for a
+ * stream that is not in global-index terms — a file other than the last
+ * that does not hold MaxFileSize / 16 labels, or more labels than
+ * NumUnits * LabelsPerUnit (sharded dirs); then cfg as post_prove looks at
+ * it, POST_ERR_NO_GPU included. */
+int post_prove_healed(const char *data_dir, const PostProveConfig *cfg,
+                      const PostHealConfig *heal, PostProof *out,
+                      uint64_t *bad_pages, uint32_t cap, PostHealReport *r);
+
+/* The same pass with no proof: check the seal, recompute the bad pages,
+ * write the confirmed ones back.  A following post_check_seal is clean
+ * exactly when pages_written == pages_bad.  hits_* and the proof flags stay
+ * zero.  Validated as post_prove_healed, then POST_ERR_NO_GPU. */
+int post_repair_data(const char *data_dir, uint32_t provider_id,
+                     const PostHealConfig *heal, uint64_t *bad_pages,
+                     uint32_t cap, PostHealReport *r);
+
 /* ---------- introspection / self-test ---------- */
 /* Engine's independent blake3 (for cross-checking vs the oracle's in
  * tests; not a product entry point). */

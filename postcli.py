@@ -13,13 +13,15 @@ verification, provider listing and benchmarking
         --num-units U [--labels-per-unit L] [--scrypt-n N] \
         [--max-file-size B] [--shard R/W]
     python postcli.py prove --datadir DIR --challenge HEX32 [--nonces 288] \
-        [--check-seal [--max-report N]]
+        [--check-seal [--max-report N] \
+         [--heal [--write-back] [--max-heal-pages N]]]
     python postcli.py verify --datadir DIR --proof proof.json \
         [--k3 K] [--seed HEX]
     python postcli.py verify-data --datadir DIR [--every K | --fraction PCT] \
         [--seed S] [--shard R/W | --from I --to J] [--max-report N]
     python postcli.py seal --datadir DIR
     python postcli.py check-seal --datadir DIR [--max-report N]
+    python postcli.py repair --datadir DIR [--max-heal-pages N]
 
 init resumes automatically from existing postdata_*.bin
 (activation/post.go:267-271); --shard R/W initializes only rank R of W
@@ -35,6 +37,15 @@ pages as label ranges and exits with status 1 when there is one; prove
 --check-seal does the same check during the proving pass itself, prints the
 ranges on stderr as ready verify-data commands, and withholds a proof that
 has an index in a bad page (exit status 1).
+
+prove --check-seal --heal puts the bad pages right in the same call (DESIGN
+§3.6): they are recomputed on the GPU, their hits replaced, and the proof is
+the one the undamaged dir gives; --write-back also writes the pages the seal
+confirms over the file bytes.  The proof is withheld (exit status 1) when it
+has an index in a page the seal could not confirm, or when more than
+--max-heal-pages pages are bad and nothing was healed.  repair is the same
+pass without a proof: it writes the confirmed pages back and exits with
+status 0 when a following check-seal would be clean.
 """
 import argparse
 import base64
@@ -139,7 +150,43 @@ def cmd_prove(args):
     if args.pow_difficulty:
         cfg.pow_difficulty = bytes.fromhex(args.pow_difficulty)
     t0 = time.time()
-    if args.check_seal:
+    if not args.heal and (args.write_back or args.max_heal_pages):
+        raise SystemExit("--write-back and --max-heal-pages need --heal")
+    if args.heal:
+        if not args.check_seal:
+            raise SystemExit("--heal needs --check-seal")
+        try:
+            proof, rep = gsm_amd.prove_healed(
+                args.datadir, bytes.fromhex(args.challenge), cfg,
+                gsm_amd.ProveOpts(nonces=args.nonces),
+                heal=gsm_amd.HealOpts(max_pages=args.max_heal_pages,
+                                      write_back=args.write_back),
+                max_report=args.max_report)
+        except gsm_amd.EngineError as e:
+            print(f"prove failed: {e}", file=sys.stderr)
+            return 2
+        if rep.heal_skipped:
+            print(f"seal: {rep.pages_bad} of {rep.pages} pages differ from "
+                  "postdata_seal.bin, more than --max-heal-pages: nothing "
+                  "healed; confirm with", file=sys.stderr)
+            for a, b in rep.bad_label_ranges():
+                print(f"  verify-data --datadir {args.datadir} --every 1 "
+                      f"--from {a} --to {b}", file=sys.stderr)
+        elif not rep.clean:
+            for a, b in rep.bad_label_ranges():
+                print(f"healed labels [{a}, {b})", file=sys.stderr)
+            print(f"seal: {rep.pages_bad} of {rep.pages} pages differed, "
+                  f"{rep.pages_healed} recomputed "
+                  f"({rep.labels_repaired} labels differed on disk), "
+                  f"{rep.pages_unconfirmed} not confirmed by the seal, "
+                  f"{rep.pages_written} written back", file=sys.stderr)
+        if not rep.publishable:
+            print("the proof has an index in a bad page: not printed, do "
+                  "not publish" if not rep.heal_skipped else
+                  "the bad pages were not healed: the proof is not printed, "
+                  "do not publish", file=sys.stderr)
+            return 1
+    elif args.check_seal:
         try:
             proof, rep = gsm_amd.prove_checked(
                 args.datadir, bytes.fromhex(args.challenge), cfg,
@@ -200,6 +247,29 @@ def cmd_check_seal(args):
         "seconds": round(time.time() - t0, 2),
     }))
     return 0 if rep.clean else 1
+
+
+def cmd_repair(args):
+    t0 = time.time()
+    try:
+        rep = gsm_amd.repair_data(
+            args.datadir, gsm_amd.HealOpts(max_pages=args.max_heal_pages),
+            args.provider, args.max_report)
+    except gsm_amd.EngineError as e:
+        print(f"repair failed: {e}", file=sys.stderr)
+        return 2
+    print(json.dumps({
+        "total_labels": rep.total_labels, "pages": rep.pages,
+        "pages_bad": rep.pages_bad, "pages_healed": rep.pages_healed,
+        "pages_written": rep.pages_written,
+        "pages_unconfirmed": rep.pages_unconfirmed,
+        "labels_repaired": rep.labels_repaired,
+        "heal_skipped": rep.heal_skipped,
+        "bad": [{"page": p, "from": a, "to": b} for p, (a, b)
+                in zip(rep.bad_pages, rep.bad_label_ranges())],
+        "seconds": round(time.time() - t0, 2),
+    }))
+    return 0 if rep.repaired else 1
 
 
 def cmd_verify(args):
@@ -332,6 +402,13 @@ def build_parser():
     p.add_argument("--check-seal", action="store_true",
                    help="check postdata_seal.bin in the same pass")
     p.add_argument("--max-report", type=int, default=64)
+    p.add_argument("--heal", action="store_true",
+                   help="with --check-seal: recompute the bad pages and "
+                        "prove over the recomputed labels")
+    p.add_argument("--write-back", action="store_true",
+                   help="with --heal: write confirmed pages to the files")
+    p.add_argument("--max-heal-pages", type=int, default=0,
+                   help="with --heal: heal at most N pages (default 4096)")
     p.set_defaults(fn=cmd_prove)
     s = sub.add_parser("seal")
     s.add_argument("--datadir", required=True)
@@ -342,6 +419,12 @@ def build_parser():
     c.add_argument("--provider", type=int, default=0)
     c.add_argument("--max-report", type=int, default=64)
     c.set_defaults(fn=cmd_check_seal)
+    r = sub.add_parser("repair")
+    r.add_argument("--datadir", required=True)
+    r.add_argument("--provider", type=int, default=0)
+    r.add_argument("--max-heal-pages", type=int, default=0)
+    r.add_argument("--max-report", type=int, default=64)
+    r.set_defaults(fn=cmd_repair)
     v = sub.add_parser("verify")
     v.add_argument("--datadir", required=True)
     v.add_argument("--proof", required=True)
