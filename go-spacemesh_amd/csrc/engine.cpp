@@ -287,11 +287,17 @@ struct PostInitSession {
   double last_kernel_ms = 0; /* accumulated over the last post_init_step */
 
   /* split-kernel init path (init_step_split): 0 = monolithic ROMix on
-   * `stream`; 2 = phase-mixed, the two halves of the slots on `stream` and
-   * `stream_b`; 1 = the split kernels on `stream` alone (measurement).
+   * `stream`; 2 or 3 = phase-mixed, the slots divided among `stream`,
+   * `stream_b` (and `stream_c`); 1 = the split kernels on `stream` alone
+   * (measurement).  `split_chain` holds the fill of a unit behind the fill
+   * of the unit before it (two streams only, the earlier schedule, A/B).
    * Buffer set 1 and `copy_stream` double-buffer what the host reads, so
    * batch i is processed while batch i+1 runs. */
   int split_streams = 0;
+  bool split_chain = false;
+  uint64_t unit_cursor = 0; /* units issued so far: unit u runs on stream
+                               u % split_streams, across batches and calls */
+  uint64_t split_batch_no = 0; /* batches issued so far: output set = & 1 */
   uint32_t cand_cap = 0;
   uint8_t *d_out1 = nullptr;
   PostVrfCandidate *d_cand1 = nullptr;
@@ -299,25 +305,30 @@ struct PostInitSession {
   uint8_t *h_batch1 = nullptr;                       /* pinned */
   PostVrfCandidate *h_cand[2] = {nullptr, nullptr};  /* pinned */
   unsigned int *h_cand_count = nullptr;              /* pinned, 2 entries */
-  hipStream_t stream_b = nullptr, copy_stream = nullptr;
-  hipEvent_t ev_fill[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_tail[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  hipStream_t stream_b = nullptr, stream_c = nullptr, copy_stream = nullptr;
+  hipEvent_t ev_fill[4] = {nullptr, nullptr, nullptr, nullptr}; /* chain */
+  hipEvent_t ev_tail[2][3] = {{nullptr, nullptr, nullptr},
+                              {nullptr, nullptr, nullptr}};
   hipEvent_t ev_end[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+  hipEvent_t ev_reset[2] = {nullptr, nullptr}; /* count of set i zeroed */
 
   ~PostInitSession() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (stream_b) (void)hipStreamSynchronize(stream_b);
+    if (stream_c) (void)hipStreamSynchronize(stream_c);
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);
     for (int i = 0; i < 4; i++)
       if (ev_fill[i]) (void)hipEventDestroy(ev_fill[i]);
     for (int i = 0; i < 2; i++) {
-      for (int k = 0; k < 2; k++)
+      for (int k = 0; k < 3; k++)
         if (ev_tail[i][k]) (void)hipEventDestroy(ev_tail[i][k]);
+      if (ev_reset[i]) (void)hipEventDestroy(ev_reset[i]);
       if (ev_end[i]) (void)hipEventDestroy(ev_end[i]);
       if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
       if (h_cand[i]) (void)hipHostFree(h_cand[i]);
     }
     if (stream_b) (void)hipStreamDestroy(stream_b);
+    if (stream_c) (void)hipStreamDestroy(stream_c);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (d_out1) (void)hipFree(d_out1);
     if (d_cand1) (void)hipFree(d_cand1);
@@ -428,8 +439,14 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
    * workgroups only queue (grid-stride covers the batch regardless) */
   lanes = std::min<uint64_t>(lanes,
                              poste_label_resident_slots(s->gap_shift));
-  lanes = (lanes / 128) * 128; /* keep the dual-stream grid block-aligned */
-  if (lanes == 0) lanes = 128;
+  /* keep the dual-stream grid block-aligned; the three-stream schedule
+   * rounds its thirds to whole workgroups itself and needs whole
+   * workgroups only */
+  const char *const mx = getenv("POST_ROMIX_MIX");
+  const bool want3 = !mx || !*mx || std::strcmp(mx, "free3") == 0;
+  const uint64_t lane_round = want3 ? 64 : 128;
+  lanes = (lanes / lane_round) * lane_round;
+  if (lanes < 128) lanes = 128;
   if (lanes == 0) {
     set_error("not enough device memory for one scratch lane block");
     return POST_ERR_OOM;
@@ -445,9 +462,9 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
   }
   HIP_TRY(hipMalloc(&s->d_out, (size_t)s->batch * POST_LABEL_SIZE));
   /* The tail appends one candidate per workgroup per launch, whatever the
-   * threshold.  The split path launches one tail per unit of at most
-   * lanes/2 labels, so a batch appends at most batch/64 plus one ragged
-   * workgroup per unit (at most 8 units) — also when the threshold it was
+   * threshold.  The split path launches one tail per unit; units are whole
+   * workgroups but for the last of a batch, so a batch appends at most
+   * batch/64 plus one ragged workgroup — also when the threshold it was
    * given lags the host's by the batches in flight. */
   s->cand_cap =
       (uint32_t)std::max<uint64_t>(CAND_CAP, s->batch / 64 + 16);
@@ -459,20 +476,27 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
   HIP_TRY(hipHostMalloc(&s->h_batch, (size_t)s->batch * POST_LABEL_SIZE));
   HIP_TRY(hipStreamCreate(&s->stream));
 
-  /* POST_ROMIX_MIX: unset = phase-mixed wherever the lean gap-1 kernel
-   * applies; 0 = the monolithic kernel on one stream (A/B, fallback);
-   * seq = the split kernels back to back on one stream (measures the
-   * phases apart: profiles/r04_romix_phases.md) */
+  /* POST_ROMIX_MIX: unset or free3 = phase-mixed wherever the lean gap-1
+   * kernel applies, three free-running streams over thirds of the slots
+   * (two over halves below 192 slots); free2 = two free-running streams;
+   * chain = two streams with the fill-behind-fill wait of the earlier
+   * schedule (both A/B: profiles/r05_freerun.md); 0 = the monolithic
+   * kernel on one stream (A/B, fallback); seq = the split kernels back to
+   * back on one stream (measures the phases apart:
+   * profiles/r04_romix_phases.md) */
   {
-    const char *mx = getenv("POST_ROMIX_MIX");
     const bool lean = poste_label_romix_lean_ok(cfg->scrypt_n, s->gap_shift,
                                                 lanes) != 0;
     if (!lean || (mx && std::strcmp(mx, "0") == 0))
       s->split_streams = 0;
     else if (mx && std::strcmp(mx, "seq") == 0)
       s->split_streams = 1;
+    else if (want3 && lanes >= 192)
+      s->split_streams = 3;
     else
       s->split_streams = lanes >= 128 ? 2 : 0;
+    s->split_chain =
+        s->split_streams == 2 && mx && std::strcmp(mx, "chain") == 0;
   }
   if (s->split_streams) {
     if (!s->keep_all)
@@ -486,13 +510,20 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
                             sizeof(PostVrfCandidate) * s->cand_cap));
       HIP_TRY(hipEventCreate(&s->ev_end[i]));
       HIP_TRY(hipEventCreateWithFlags(&s->ev_done[i], hipEventDisableTiming));
-      for (int k = 0; k < 2; k++)
+      HIP_TRY(hipEventCreateWithFlags(&s->ev_reset[i],
+                                      hipEventDisableTiming));
+      for (int k = 0; k < s->split_streams; k++)
         HIP_TRY(hipEventCreateWithFlags(&s->ev_tail[i][k],
                                         hipEventDisableTiming));
     }
-    for (int i = 0; i < 4; i++)
-      HIP_TRY(hipEventCreateWithFlags(&s->ev_fill[i], hipEventDisableTiming));
-    if (s->split_streams == 2) HIP_TRY(hipStreamCreate(&s->stream_b));
+    if (s->split_chain)
+      for (int i = 0; i < 4; i++)
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_fill[i],
+                                        hipEventDisableTiming));
+    /* with the copy stream at most four streams: the hardware queues a
+     * process gets by default */
+    if (s->split_streams >= 2) HIP_TRY(hipStreamCreate(&s->stream_b));
+    if (s->split_streams >= 3) HIP_TRY(hipStreamCreate(&s->stream_c));
     HIP_TRY(hipStreamCreate(&s->copy_stream));
   }
 
@@ -723,12 +754,21 @@ static int write_metadata(PostInitSession *s) {
 /* Init step on the split ROMix kernels (lean gap-1 geometry only).
  *
  * The slots are divided among split_streams streams (two halves when
- * phase-mixed).  Work is issued in units of at most one half of the slots:
- * prologue -> fill -> mix -> tail, units alternating between the streams,
- * and the fill of unit u waits for the fill of unit u-1 on the other
- * stream.  That holds stream B one phase behind stream A for the whole
- * call: while one half of the chip's waves streams writes, the other half
- * random-reads, and the event chain never lets them fall back into step.
+ * phase-mixed, thirds rounded down to whole workgroups with free3), and
+ * `xbuf` alike.  Work is issued in units of at most one such share:
+ * prologue -> fill -> mix -> tail, units going round the streams.  Each
+ * stream runs its own chain over its own slots and no ROMix kernel waits
+ * for another stream: a stream's next fill starts when its previous tail
+ * ends, beside whatever the others run (any mixture of fills and mixes),
+ * so the chip stays full for the whole call.  Stream order alone protects a
+ * slot column (a mix follows its own fill, the next fill its own mix).
+ * What streams share is ordered by events, each stated where it is
+ * enforced: the batch's candidate count (ev_reset), the outputs the copy
+ * stream reads (ev_tail), and the output sets the host hands back
+ * (ev_done).  POST_ROMIX_MIX=chain keeps the earlier schedule for A/B: the
+ * fill of unit u waits for the fill of unit u-1 on the other stream, which
+ * held the streams one phase apart and left the chip half empty while the
+ * longer fill finished (profiles/r05_freerun.md).
  *
  * Batches (s->batch labels, as on the monolithic path) only group what the
  * host reads.  Their outputs are double-buffered and copied by
@@ -740,13 +780,19 @@ static int write_metadata(PostInitSession *s) {
 static int init_step_split(PostInitSession *s, uint64_t max_labels,
                            uint64_t *done) {
   const int ns = s->split_streams;
-  const uint64_t unit = s->lanes / (uint64_t)ns; /* slots per unit */
-  hipStream_t st[2] = {s->stream, s->stream_b};
+  /* slots per unit: one stream's share, whole 64-quad workgroups */
+  const uint64_t unit = s->lanes / (uint64_t)ns / 64 * 64;
+  hipStream_t st[3] = {s->stream, s->stream_b, s->stream_c};
   uint8_t *const d_outs[2] = {s->d_out, s->d_out1};
   uint8_t *const h_batches[2] = {s->h_batch, s->h_batch1};
   PostVrfCandidate *const d_cands[2] = {s->d_cand, s->d_cand1};
   unsigned int *const d_counts[2] = {s->d_cand_count, s->d_cand_count1};
 
+  /* End of call, cancel and error all leave through here: every stream is
+   * synchronised on its own, so nothing relies on one stream's end
+   * implying another's.  Every event a stream waits for is recorded before
+   * the wait is queued, so a call that fails half-way through issue()
+   * leaves no stream waiting for a record that never comes. */
   auto drain = [&] {
     for (int k = 0; k < ns; k++) (void)hipStreamSynchronize(st[k]);
     (void)hipStreamSynchronize(s->copy_stream);
@@ -795,50 +841,76 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
     int set = 0;
     bool live = false;
   };
-  uint64_t unit_seq = 0; /* units issued in this call */
-  uint64_t batch_no = 0;
+  uint64_t issued = 0; /* units issued in this call */
   int last_set = -1;
 
   /* queue one batch: its units on the compute streams, its copies on
    * copy_stream behind the last tail of each stream */
   auto issue = [&](Batch &b) -> int {
-    b.set = (int)(batch_no++ & 1);
+    /* Output set b.set was last used by the batch two before this one.
+     * The host has passed hipEventSynchronize(ev_done) of that batch
+     * (process() runs before the next issue()), and ev_done follows every
+     * tail and every copy of it, so its buffers, its count and its events
+     * (ev_tail, ev_reset, ev_end, ev_done) are free to use again on any
+     * stream.  Sets and the stream cursor carry on across calls; a call
+     * ends drained, so the first batch of a call may start on any stream. */
+    b.set = (int)(s->split_batch_no++ & 1);
     b.max_cand = 0;
     uint8_t *out =
         s->keep_all ? s->d_all + b.pos * POST_LABEL_SIZE : d_outs[b.set];
     args.cand = d_cands[b.set];
     args.cand_count = d_counts[b.set];
     difficulty_to_be_words(cur_difficulty, args.difficulty_be);
-    /* the other stream's first tail of this batch follows its fill, which
-     * waits for this stream's fill: ordered behind the reset */
+    /* The batch's candidate count is zeroed on the stream of its first
+     * unit, whose tails follow in stream order.  Every other stream's
+     * tails append to the same count and nothing else orders them behind
+     * the reset (this stream may still be busy with the batch before), so
+     * each of them waits for ev_reset before its first tail of the batch. */
+    const int k0 = (int)(s->unit_cursor % (uint64_t)ns);
     SPLIT_TRY(hipMemsetAsync(d_counts[b.set], 0, sizeof(unsigned int),
-                             st[unit_seq % ns]));
-    bool used[2] = {false, false};
-    for (uint64_t off = 0; off < b.count; off += unit) {
-      const int k = (int)(unit_seq % (uint64_t)ns);
-      const uint64_t c = std::min(unit, b.count - off);
+                             st[k0]));
+    if (ns > 1) SPLIT_TRY(hipEventRecord(s->ev_reset[b.set], st[k0]));
+    /* units of equal size, whole workgroups: a ragged batch costs every
+     * unit a few labels, not one more round for a handful of them */
+    const uint64_t nunits = (b.count + unit - 1) / unit;
+    const uint64_t per = ((b.count + nunits - 1) / nunits + 63) / 64 * 64;
+    bool used[3] = {false, false, false};
+    for (uint64_t off = 0; off < b.count; off += per) {
+      const int k = (int)(s->unit_cursor % (uint64_t)ns);
+      const uint64_t c = std::min(per, b.count - off);
       const uint32_t blocks = (uint32_t)((c + 63) / 64);
       args.start = s->range_start + b.pos + off;
       args.count = c;
+      /* stream k owns slots and xbuf tasks [k * unit, (k + 1) * unit) */
       args.xbuf = s->d_xbuf + (uint64_t)k * unit * 32; /* 128 B per task */
       args.out = out + off * POST_LABEL_SIZE;
       ph.xbuf = args.xbuf;
       ph.slot_base = (uint64_t)k * unit;
       ph.count = c;
-      if (unit_seq == 0) SPLIT_TRY(hipEventRecord(s->ev0, st[k]));
+      /* the streams are idle when a call begins and this unit is queued
+       * first, so ev0 marks the start of the call's first kernel */
+      if (issued == 0) SPLIT_TRY(hipEventRecord(s->ev0, st[k]));
       SPLIT_TRY(poste_launch_label_prologue(&args, blocks, st[k]));
-      if (ns == 2 && unit_seq > 0)
-        SPLIT_TRY(hipStreamWaitEvent(st[k], s->ev_fill[(unit_seq - 1) & 3],
-                                     0));
+      if (s->split_chain && issued > 0)
+        SPLIT_TRY(hipStreamWaitEvent(
+            st[k], s->ev_fill[(s->unit_cursor - 1) & 3], 0));
       SPLIT_TRY(poste_launch_romix_fill(&ph, st[k]));
-      if (ns == 2)
-        SPLIT_TRY(hipEventRecord(s->ev_fill[unit_seq & 3], st[k]));
+      if (s->split_chain)
+        SPLIT_TRY(hipEventRecord(s->ev_fill[s->unit_cursor & 3], st[k]));
       SPLIT_TRY(poste_launch_romix_mix(&ph, st[k]));
+      if (k != k0 && !used[k])
+        SPLIT_TRY(hipStreamWaitEvent(st[k], s->ev_reset[b.set], 0));
       SPLIT_TRY(poste_launch_label_tail(&args, blocks, st[k]));
       b.max_cand += blocks;
       used[k] = true;
-      unit_seq++;
+      s->unit_cursor++;
+      issued++;
     }
+    /* The copy stream reads the batch behind the last tail of every stream
+     * that had a unit of it.  It is in order, so ev_end, recorded once
+     * those waits are queued, also follows the tails of every earlier
+     * batch: with ev0 it brackets the call whichever streams ran the first
+     * and the last unit. */
     for (int k = 0; k < ns; k++) {
       if (!used[k]) continue;
       SPLIT_TRY(hipEventRecord(s->ev_tail[b.set][k], st[k]));
@@ -935,6 +1007,8 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
   int cur = 0;
   bool cancelled = false;
   while (pos < target) {
+    /* cancel is seen between batches only: a batch is either issued whole,
+     * with all its events, or not at all */
     if (s->cancel.load()) {
       cancelled = true;
       break;

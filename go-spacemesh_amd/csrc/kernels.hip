@@ -456,8 +456,11 @@ post_label_romix_kernel(LabelKernelArgs a) {
  * task per quad and no loop over rounds: fill must have ended before mix
  * starts, and the next round's fill may only follow this round's mix, which
  * stream order provides.  X round-trips through xbuf once more, 256 B per
- * label.  Two launches on different column ranges can run side by side, one
- * writing while the other reads (engine.cpp, phase-mixed init). */
+ * label.  Launches on different column ranges can run side by side in any
+ * combination, fill beside mix, fill beside fill or mix beside mix: the
+ * init path gives each stream its own columns and lets the streams run
+ * free, with no wait between the ROMix kernels of different streams
+ * (engine.cpp, init_step_split). */
 __global__ void __launch_bounds__(POSTE_THREADS, 8)
 post_label_romix_fill_kernel(RomixPhaseArgs a) {
   const unsigned long long lane =
