@@ -38,8 +38,10 @@ from .api import (  # noqa: F401
     prove_healed,
     repair_data,
     sample_indices,
+    seal_assemble,
     seal_data,
     seal_digest_buffer,
+    seal_digest_stream,
     verify_data,
     verify_data_buffer,
 )
@@ -49,6 +51,7 @@ __all__ = [
     "PostProofMetadata", "PostSetupManager", "PostSetupOpts", "PostVerifier",
     "ProveOpts", "SealReport", "VerifyOpts", "check_seal", "events",
     "load_engine", "prove_checked", "prove_healed", "repair_data",
-    "sample_indices", "seal_data",
-    "seal_digest_buffer", "verify_data", "verify_data_buffer",
+    "sample_indices", "seal_assemble", "seal_data",
+    "seal_digest_buffer", "seal_digest_stream", "verify_data",
+    "verify_data_buffer",
 ]

@@ -212,6 +212,12 @@ def load_engine() -> ctypes.CDLL:
                 c_uint64, POINTER(c_uint64)]),
             "post_seal_data": (c_int, [c_char_p, c_uint32,
                                        POINTER(_CSealReport)]),
+            "post_init_enable_seal": (c_int, [c_void_p]),
+            "post_seal_assemble": (c_int, [c_char_p, POINTER(c_uint64)]),
+            "post_seal_digest_stream": (c_int, [
+                ctypes.c_char_p, c_uint64, c_uint64, POINTER(c_uint64),
+                c_uint32, c_uint32, c_uint32, ctypes.c_char_p, c_uint64,
+                POINTER(c_uint64)]),
             "post_check_seal": (c_int, [c_char_p, c_uint32,
                                         POINTER(c_uint64), c_uint32,
                                         POINTER(_CSealReport)]),
@@ -268,6 +274,7 @@ class PostSetupOpts:
     index_start: int = 0                # shard range
     index_end: int = 0
     scratch_bytes: int = 0
+    seal: bool = False                  # seal during init
 
 
 @dataclasses.dataclass
@@ -434,6 +441,12 @@ class PostSetupManager:
         self.engine._check(self.engine.lib.post_init_new(byref(c),
                                                          byref(handle)))
         self._session = handle
+        if self.opts.seal:
+            rc = self.engine.lib.post_init_enable_seal(handle)
+            if rc != 0:
+                err = self.engine.lib.post_last_error().decode()
+                self.reset()
+                raise EngineError(rc, err)
         self.state = self.PREPARED
 
     def start_session(self) -> None:
@@ -595,6 +608,36 @@ def seal_digest_buffer(labels: bytes, provider_id: int = 0) -> bytes:
     eng._check(eng.lib.post_seal_digest_buffer(labels, count, provider_id,
                                                out, cap, byref(n)))
     return out.raw[:n.value * 16]
+
+
+def seal_digest_stream(labels: bytes, first_index: int = 0, cuts=(),
+                       stream_end: bool = True,
+                       provider_id: int = 0) -> bytes:
+    """Page digests of a label stream that starts at first_index (a
+    multiple of 1024) and reaches the GPU cut into segments at `cuts`
+    (positions within the buffer), as init batches do.  With
+    stream_end the buffer's end closes a ragged last page."""
+    eng = Engine()
+    count = len(labels) // LABEL_SIZE
+    pages = -(-count // 1024)
+    out = ctypes.create_string_buffer(max(1, pages) * 16)
+    n = c_uint64(0)
+    cuts = list(cuts)
+    arr = (c_uint64 * max(1, len(cuts)))(*cuts)
+    eng._check(eng.lib.post_seal_digest_stream(
+        labels, count, first_index, arr, len(cuts), 1 if stream_end else 0,
+        provider_id, out, pages, byref(n)))
+    return out.raw[:n.value * 16]
+
+
+def seal_assemble(data_dir: str) -> int:
+    """Put the part files of a sealed init together into postdata_seal.bin
+    (host only); returns the page count.  EngineError(IO) names the first
+    missing page range while a shard is unfinished."""
+    eng = Engine()
+    pages = c_uint64(0)
+    eng._check(eng.lib.post_seal_assemble(data_dir.encode(), byref(pages)))
+    return pages.value
 
 
 def seal_data(data_dir: str, provider_id: int = 0) -> SealReport:

@@ -14,6 +14,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <dirent.h>
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <sys/types.h>
@@ -312,6 +313,22 @@ struct PostInitSession {
   hipEvent_t ev_end[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
   hipEvent_t ev_reset[2] = {nullptr, nullptr}; /* count of set i zeroed */
 
+  /* seal during init (post_init_enable_seal); all unused and
+   * nothing of it queued while seal_on is false */
+  bool stepped = false;      /* a post_init_step has begun */
+  bool seal_on = false;
+  int seal_fd = -1;          /* the part file */
+  uint64_t seal_first_page = 0;
+  uint64_t seal_pos = 0;     /* relative position the device carry stands at */
+  uint64_t seal_launches = 0; /* carry in = launches & 1, out = the other */
+  SealCarry *d_seal_carry = nullptr;                 /* two */
+  uint4 *d_seal_dig[2] = {nullptr, nullptr};         /* per output set */
+  uint8_t *h_seal_dig[2] = {nullptr, nullptr};       /* pinned */
+  /* POST_SEAL_DEBUG: the stream kernel timed per batch, printed at the end */
+  hipEvent_t ev_seal[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  double seal_ms = 0, seal_ms_max = 0;
+  uint64_t seal_timed = 0;
+
   ~PostInitSession() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (stream_b) (void)hipStreamSynchronize(stream_b);
@@ -345,6 +362,15 @@ struct PostInitSession {
     if (d_cand_count) (void)hipFree(d_cand_count);
     if (d_xbuf) (void)hipFree(d_xbuf);
     if (h_batch) (void)hipHostFree(h_batch);
+    if (d_seal_carry) (void)hipFree(d_seal_carry);
+    for (int i = 0; i < 2; i++) {
+      if (d_seal_dig[i]) (void)hipFree(d_seal_dig[i]);
+      if (h_seal_dig[i]) (void)hipHostFree(h_seal_dig[i]);
+    }
+    for (int i = 0; i < 2; i++)
+      for (int k = 0; k < 2; k++)
+        if (ev_seal[i][k]) (void)hipEventDestroy(ev_seal[i][k]);
+    if (seal_fd >= 0) (void)::close(seal_fd);
   }
 };
 
@@ -751,6 +777,232 @@ static int write_metadata(PostInitSession *s) {
   return POST_OK;
 }
 
+/* ------------------------- seal during init -------------------------
+ *
+ * DESIGN 3.7.  The session hashes every batch where the tail kernel left
+ * it, with post_seal_stream_kernel, and appends the digests of the pages
+ * that closed to postdata_seal.part-<index_start> once the batch's labels
+ * are in the files.  All of it hangs off seal_on: a session that never
+ * called post_init_enable_seal queues and waits for exactly what it did
+ * before. */
+static const char SEALP_MAGIC[8] = {'P', 'S', 'T', 'S', 'E', 'A', 'L', 'P'};
+constexpr uint64_t SEALP_HEADER = 32;
+constexpr uint64_t SEALP_PAGE = POSTE_SEAL_PAGE_LABELS;
+constexpr uint64_t SEALP_DIGEST = 16;
+
+static void put_le(uint8_t *p, uint64_t v, int bytes);
+static uint64_t get_le(const uint8_t *p, int bytes);
+static int seal_assemble(const char *data_dir, uint64_t *pages, bool quiet);
+
+static std::string seal_part_path(const std::string &dir, uint64_t start) {
+  return dir + "/postdata_seal.part-" + std::to_string(start);
+}
+
+/* pages of the session's range */
+static uint64_t seal_range_pages(const PostInitSession *s) {
+  return (s->range_end + SEALP_PAGE - 1) / SEALP_PAGE - s->seal_first_page;
+}
+
+/* Queue the stream kernel over the batch at relative position pos that lies
+ * at d_labels, and the copy of its digests to the pinned buffer of `set`. */
+static int seal_launch(PostInitSession *s, hipStream_t stream, int set,
+                       uint64_t pos, uint64_t count, const uint8_t *d_labels) {
+  SealStreamArgs a;
+  a.labels = (const uint4 *)d_labels;
+  a.g0 = s->range_start + pos;
+  a.count = count;
+  a.stream_end = (uint64_t)s->cfg.num_units * s->cfg.labels_per_unit;
+  a.carry_in = s->d_seal_carry + (s->seal_launches & 1);
+  a.carry_out = s->d_seal_carry + ((s->seal_launches + 1) & 1);
+  a.digests = s->d_seal_dig[set];
+  if (s->ev_seal[set][0]) HIP_TRY(hipEventRecord(s->ev_seal[set][0], stream));
+  HIP_TRY(poste_launch_seal_stream_kernel(&a, stream));
+  if (s->ev_seal[set][1]) HIP_TRY(hipEventRecord(s->ev_seal[set][1], stream));
+  s->seal_launches++;
+  s->seal_pos = pos + count;
+  const uint64_t lanes =
+      (a.g0 + count - 1) / SEALP_PAGE - a.g0 / SEALP_PAGE + 1;
+  HIP_TRY(hipMemcpyAsync(s->h_seal_dig[set], s->d_seal_dig[set],
+                         lanes * SEALP_DIGEST, hipMemcpyDeviceToHost, stream));
+  return POST_OK;
+}
+
+/* The batch's labels are in the files: append the digests of the pages that
+ * closed in it.  The caller advances `written` only after this. */
+static int seal_commit(PostInitSession *s, int set, uint64_t pos,
+                       uint64_t count) {
+  const uint64_t g0 = s->range_start + pos, end = g0 + count;
+  const uint64_t total = (uint64_t)s->cfg.num_units * s->cfg.labels_per_unit;
+  const uint64_t p0 = g0 / SEALP_PAGE;
+  const uint64_t lanes = (end - 1) / SEALP_PAGE - p0 + 1;
+  const uint64_t closed =
+      (end % SEALP_PAGE == 0 || end == total) ? lanes : lanes - 1;
+  const size_t want = (size_t)(closed * SEALP_DIGEST);
+  float ms = 0;
+  if (s->ev_seal[set][0] &&
+      hipEventElapsedTime(&ms, s->ev_seal[set][0], s->ev_seal[set][1]) ==
+          hipSuccess) {
+    s->seal_ms += ms;
+    s->seal_ms_max = std::max<double>(s->seal_ms_max, ms);
+    s->seal_timed++;
+  }
+  const off_t at =
+      (off_t)(SEALP_HEADER + (p0 - s->seal_first_page) * SEALP_DIGEST);
+  size_t put = 0;
+  while (put < want) {
+    const ssize_t w =
+        ::pwrite(s->seal_fd, s->h_seal_dig[set] + put, want - put, at + put);
+    if (w <= 0) {
+      if (w < 0 && errno == EINTR) continue;
+      set_error("short write to " +
+                seal_part_path(s->data_dir, s->range_start));
+      return POST_ERR_IO;
+    }
+    put += (size_t)w;
+  }
+  /* the range is complete: assemble, unless other shards are still open */
+  if (end == s->range_end) {
+    (void)::close(s->seal_fd);
+    s->seal_fd = -1;
+    if (s->seal_timed)
+      std::fprintf(stderr,
+                   "seal: %llu batches of up to %llu labels, stream kernel "
+                   "%.3f ms per batch (max %.3f ms, %.1f ms in all)\n",
+                   (unsigned long long)s->seal_timed,
+                   (unsigned long long)s->batch, s->seal_ms / s->seal_timed,
+                   s->seal_ms_max, s->seal_ms);
+    return seal_assemble(s->data_dir.c_str(), nullptr, true);
+  }
+  return POST_OK;
+}
+
+/* A call that failed may have left the device carry ahead of `written`
+ * (the batch behind the failing one was already queued) or the part file
+ * ahead of it.  Fall back to the page boundary, as a new session would. */
+static int seal_resync(PostInitSession *s) {
+  const uint64_t w = s->written.load();
+  if (s->seal_pos == w || s->seal_fd < 0) return POST_OK;
+  const uint64_t pos = w / SEALP_PAGE * SEALP_PAGE;
+  if (::ftruncate(s->seal_fd,
+                  (off_t)(SEALP_HEADER + pos / SEALP_PAGE * SEALP_DIGEST)) !=
+      0) {
+    set_error("cannot truncate " +
+              seal_part_path(s->data_dir, s->range_start));
+    return POST_ERR_IO;
+  }
+  s->written.store(pos);
+  s->seal_pos = pos;
+  return POST_OK;
+}
+
+int post_init_enable_seal(PostInitSession *s) {
+  if (!s || s->data_dir.empty()) {
+    set_error("seal during init needs a session with a data dir");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (s->stepped) {
+    set_error("post_init_enable_seal must be called before the first step");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (s->seal_on) return POST_OK;
+  const uint64_t total = (uint64_t)s->cfg.num_units * s->cfg.labels_per_unit;
+  const uint64_t range = s->range_end - s->range_start;
+  if (s->range_start % SEALP_PAGE != 0 ||
+      (s->range_end % SEALP_PAGE != 0 && s->range_end != total)) {
+    set_error("seal during init needs a range of whole 1024-label pages: "
+              "index_start a multiple of 1024, index_end a multiple of 1024 "
+              "or the end of the label space");
+    return POST_ERR_UNSUPPORTED;
+  }
+  if (s->cfg.max_file_size % POST_LABEL_SIZE != 0) {
+    set_error("seal during init needs a MaxFileSize that is a multiple of "
+              "16: pages are in terms of the label stream");
+    return POST_ERR_UNSUPPORTED;
+  }
+  const std::string part = seal_part_path(s->data_dir, s->range_start);
+  const std::string sidecar = s->data_dir + "/postdata_seal.bin";
+  struct stat st;
+  const bool have_part = ::stat(part.c_str(), &st) == 0;
+  const uint64_t part_size = have_part ? (uint64_t)st.st_size : 0;
+  const bool have_sidecar = ::stat(sidecar.c_str(), &st) == 0;
+  const uint64_t on_disk = s->written.load();
+  if (!have_part && on_disk > 0) {
+    if (have_sidecar && on_disk == range) return POST_OK; /* all done */
+    set_error(have_sidecar
+                  ? "postdata_seal.bin is finished but the labels of this "
+                    "range are not; finish init without a seal and run `seal`"
+                  : "dir was started without a seal; finish init and run "
+                    "`seal`");
+    return POST_ERR_UNSUPPORTED;
+  }
+
+  s->seal_first_page = s->range_start / SEALP_PAGE;
+  const uint64_t end_page = (s->range_end + SEALP_PAGE - 1) / SEALP_PAGE;
+  uint8_t hdr[SEALP_HEADER] = {0};
+  std::memcpy(hdr, SEALP_MAGIC, 8);
+  put_le(hdr + 8, SEALP_PAGE, 4);
+  put_le(hdr + 12, SEALP_DIGEST, 4);
+  put_le(hdr + 16, s->seal_first_page, 8);
+  put_le(hdr + 24, end_page, 8);
+  uint64_t resume = 0;
+  if (s->seal_fd >= 0) (void)::close(s->seal_fd); /* an earlier failed call */
+  s->seal_fd = ::open(part.c_str(), O_RDWR | O_CREAT, 0644);
+  if (s->seal_fd < 0) {
+    set_error("cannot open " + part);
+    return POST_ERR_IO;
+  }
+  if (have_part) {
+    uint8_t got[SEALP_HEADER];
+    if (part_size < SEALP_HEADER ||
+        ::pread(s->seal_fd, got, SEALP_HEADER, 0) != (ssize_t)SEALP_HEADER ||
+        std::memcmp(got, hdr, SEALP_HEADER) != 0) {
+      set_error(part + " has a header that disagrees with the session");
+      (void)::close(s->seal_fd);
+      s->seal_fd = -1;
+      return POST_ERR_IO;
+    }
+    const uint64_t pages_done = (part_size - SEALP_HEADER) / SEALP_DIGEST;
+    if (on_disk == range && pages_done >= seal_range_pages(s))
+      resume = range; /* complete; only the assembly may be missing */
+    else
+      resume = std::min(on_disk / SEALP_PAGE * SEALP_PAGE,
+                        std::min(pages_done, seal_range_pages(s)) * SEALP_PAGE);
+  } else if (::pwrite(s->seal_fd, hdr, SEALP_HEADER, 0) !=
+             (ssize_t)SEALP_HEADER) {
+    set_error("cannot write " + part);
+    return POST_ERR_IO;
+  }
+  const uint64_t keep = resume == range ? seal_range_pages(s)
+                                        : resume / SEALP_PAGE;
+  if (::ftruncate(s->seal_fd, (off_t)(SEALP_HEADER + keep * SEALP_DIGEST)) !=
+      0) {
+    set_error("cannot truncate " + part);
+    return POST_ERR_IO;
+  }
+  s->written.store(resume);
+  s->seal_pos = resume;
+  if (resume == range) {
+    (void)::close(s->seal_fd);
+    s->seal_fd = -1;
+    return seal_assemble(s->data_dir.c_str(), nullptr, true);
+  }
+
+  int rc = require_gpu(s->cfg.provider_id);
+  if (rc != POST_OK) return rc;
+  /* a batch touches at most batch / 1024 + 2 pages */
+  const size_t dig_bytes = (size_t)((s->batch / SEALP_PAGE + 2) * SEALP_DIGEST);
+  HIP_TRY(hipMalloc(&s->d_seal_carry, 2 * sizeof(SealCarry)));
+  HIP_TRY(hipMemset(s->d_seal_carry, 0, 2 * sizeof(SealCarry)));
+  for (int i = 0; i < (s->split_streams ? 2 : 1); i++) {
+    HIP_TRY(hipMalloc(&s->d_seal_dig[i], dig_bytes));
+    HIP_TRY(hipHostMalloc(&s->h_seal_dig[i], dig_bytes));
+    if (getenv("POST_SEAL_DEBUG"))
+      for (int k = 0; k < 2; k++) HIP_TRY(hipEventCreate(&s->ev_seal[i][k]));
+  }
+  s->seal_on = true;
+  return POST_OK;
+}
+
 /* Init step on the split ROMix kernels (lean gap-1 geometry only).
  *
  * The slots are divided among split_streams streams (two halves when
@@ -917,6 +1169,16 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
       SPLIT_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_tail[b.set][k], 0));
     }
     SPLIT_TRY(hipEventRecord(s->ev_end[b.set], s->copy_stream));
+    /* the seal of the batch: behind every tail of it like the copies, and
+     * behind the seal of the batch before, which left the carry */
+    if (s->seal_on) {
+      const int rc =
+          seal_launch(s, s->copy_stream, b.set, b.pos, b.count, out);
+      if (rc != POST_OK) {
+        drain();
+        return rc;
+      }
+    }
     SPLIT_TRY(hipMemcpyAsync(h_batches[b.set], out,
                              b.count * POST_LABEL_SIZE, hipMemcpyDeviceToHost,
                              s->copy_stream));
@@ -991,6 +1253,9 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
     if (rc == POST_OK && !s->data_dir.empty())
       rc = write_batch_files(s, s->range_start + b.pos, b.count,
                              h_batches[b.set]);
+    /* digests only behind their labels */
+    if (rc == POST_OK && s->seal_on)
+      rc = seal_commit(s, b.set, b.pos, b.count);
     if (rc != POST_OK) {
       drain();
       return rc;
@@ -1046,6 +1311,11 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
   *done = 0;
   int rc = require_gpu(s->cfg.provider_id);
   if (rc != POST_OK) return rc;
+  s->stepped = true;
+  if (s->seal_on) {
+    rc = seal_resync(s);
+    if (rc != POST_OK) return rc;
+  }
   if (s->split_streams) return init_step_split(s, max_labels, done);
 
   LabelKernelArgs args;
@@ -1097,6 +1367,10 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
     HIP_TRY(poste_launch_label_kernel(&args, blocks, s->stream));
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    if (s->seal_on) {
+      rc = seal_launch(s, s->stream, 0, pos, count, args.out);
+      if (rc != POST_OK) return rc;
+    }
     HIP_TRY(hipMemcpyAsync(s->h_batch, args.out, count * POST_LABEL_SIZE,
                            hipMemcpyDeviceToHost, s->stream));
     unsigned int n_cand = 0;
@@ -1176,6 +1450,10 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
     if (!s->data_dir.empty()) {
       rc = write_batch_files(s, s->range_start + pos, count, s->h_batch);
       if (rc != POST_OK) return rc;
+      if (s->seal_on) {
+        rc = seal_commit(s, 0, pos, count);
+        if (rc != POST_OK) return rc;
+      }
     }
     float ms = 0;
     (void)hipEventElapsedTime(&ms, s->ev0, s->ev1);
@@ -3117,6 +3395,252 @@ int post_repair_data(const char *data_dir, uint32_t provider_id,
   }
   heal_report(chk, w, heal_it, r);
   if (chk.pages_bad && !heal_it) r->heal_skipped = 1;
+  return POST_OK;
+}
+
+/* ------------------- seal during init: assembly ------------------- */
+
+/* One postdata_seal.part-<index_start> of a dir, header checked. */
+struct SealPart {
+  std::string path;
+  uint64_t first = 0, end = 0; /* pages [first, end) */
+  uint64_t have = 0;           /* digests in the file */
+};
+
+/* The parts of DESIGN 3.7 put together into the sidecar of 3.5.  `quiet` is
+ * the call a session makes when its own range is complete: whatever keeps
+ * the parts from being assembled (other shards still running, a damaged
+ * part of another shard) is then left for the direct call to report. */
+static int seal_assemble(const char *data_dir, uint64_t *pages, bool quiet) {
+  if (pages) *pages = 0;
+  DirMetadata md;
+  int rc = read_dir_metadata(data_dir, md);
+  if (rc != POST_OK) return quiet ? POST_OK : rc;
+  const uint64_t npages = seal_pages(md.total);
+  const std::string dir(data_dir);
+  const std::string sidecar = dir + "/postdata_seal.bin";
+  auto fail = [quiet](const std::string &msg) -> int {
+    if (quiet) return POST_OK;
+    set_error(msg);
+    return POST_ERR_IO;
+  };
+
+  static const char PREFIX[] = "postdata_seal.part-";
+  std::vector<SealPart> parts;
+  DIR *dh = ::opendir(data_dir);
+  if (!dh) return fail("cannot list " + dir);
+  std::vector<std::string> names;
+  while (struct dirent *de = ::readdir(dh)) {
+    if (std::strncmp(de->d_name, PREFIX, sizeof PREFIX - 1) == 0)
+      names.push_back(de->d_name);
+  }
+  ::closedir(dh);
+  for (const std::string &name : names) {
+    const char *num = name.c_str() + sizeof PREFIX - 1;
+    char *e = nullptr;
+    errno = 0;
+    const uint64_t start = strtoull(num, &e, 10);
+    if (*num < '0' || *num > '9' || *e != 0 || errno != 0) continue;
+    SealPart p;
+    p.path = dir + "/" + name;
+    FILE *f = std::fopen(p.path.c_str(), "rb");
+    if (!f) {
+      if (errno == ENOENT) continue; /* another shard assembled meanwhile */
+      return fail("cannot open " + p.path);
+    }
+    uint8_t hdr[SEALP_HEADER];
+    struct stat st;
+    const bool ok = fstat(fileno(f), &st) == 0 &&
+                    std::fread(hdr, 1, SEALP_HEADER, f) == SEALP_HEADER;
+    std::fclose(f);
+    if (!ok) return fail(name + " is shorter than its header");
+    if (std::memcmp(hdr, SEALP_MAGIC, 8) != 0)
+      return fail(name + " has a wrong magic");
+    if (get_le(hdr + 8, 4) != SEAL_PAGE || get_le(hdr + 12, 4) != SEAL_DIGEST)
+      return fail(name + " has an unsupported page_labels or digest_bytes");
+    p.first = get_le(hdr + 16, 8);
+    p.end = get_le(hdr + 24, 8);
+    p.have = ((uint64_t)st.st_size - SEALP_HEADER) / SEAL_DIGEST;
+    if (p.first != start / SEAL_PAGE || start % SEAL_PAGE != 0)
+      return fail(name + ": first_page " + std::to_string(p.first) +
+                  " disagrees with the file name");
+    if (p.end <= p.first || p.end > npages)
+      return fail(name + ": pages [" + std::to_string(p.first) + ", " +
+                  std::to_string(p.end) + ") lie outside the dir's " +
+                  std::to_string(npages) + " pages");
+    parts.push_back(p);
+  }
+  if (parts.empty()) {
+    /* nothing to assemble: fine when it has been done already */
+    FILE *f = std::fopen(sidecar.c_str(), "rb");
+    uint8_t hdr[SEAL_HEADER];
+    const bool done = f && std::fread(hdr, 1, SEAL_HEADER, f) == SEAL_HEADER &&
+                      std::memcmp(hdr, SEAL_MAGIC, 8) == 0 &&
+                      get_le(hdr + 16, 8) == md.total;
+    if (f) std::fclose(f);
+    if (!done)
+      return fail("no postdata_seal.part-* in " + dir +
+                  " and no finished postdata_seal.bin: pages [0, " +
+                  std::to_string(npages) + ") are missing");
+    if (pages) *pages = npages;
+    return POST_OK;
+  }
+  std::sort(parts.begin(), parts.end(),
+            [](const SealPart &a, const SealPart &b) {
+              return a.first < b.first;
+            });
+  auto missing = [](uint64_t a, uint64_t b) {
+    return "pages [" + std::to_string(a) + ", " + std::to_string(b) +
+           ") are missing";
+  };
+  uint64_t next = 0;
+  for (const SealPart &p : parts) {
+    if (p.first > next)
+      return fail("the parts leave a gap: " + missing(next, p.first));
+    if (p.first < next)
+      return fail("the parts overlap: pages [" + std::to_string(p.first) +
+                  ", " + std::to_string(std::min(next, p.end)) +
+                  ") are in more than one");
+    if (p.have < p.end - p.first)
+      return fail(p.path.substr(dir.size() + 1) + " is short, its shard is "
+                  "not finished: " + missing(p.first + p.have, p.end));
+    next = p.end;
+  }
+  if (next < npages)
+    return fail("the parts leave a gap: " + missing(next, npages));
+
+  /* as post_seal_data: temporary in the same dir, renamed into place; the
+   * name is the process's own, since two shards may finish together */
+  const std::string tmp = sidecar + ".tmp." + std::to_string((long)getpid());
+  FILE *out = std::fopen(tmp.c_str(), "wb");
+  if (!out) {
+    set_error("cannot write " + tmp);
+    return POST_ERR_IO;
+  }
+  uint8_t hdr[SEAL_HEADER] = {0};
+  std::memcpy(hdr, SEAL_MAGIC, 8);
+  put_le(hdr + 8, SEAL_PAGE, 4);
+  put_le(hdr + 12, SEAL_DIGEST, 4);
+  put_le(hdr + 16, md.total, 8);
+  rc = std::fwrite(hdr, 1, SEAL_HEADER, out) == SEAL_HEADER ? POST_OK
+                                                            : POST_ERR_IO;
+  bool vanished = false;
+  std::vector<uint8_t> buf;
+  for (size_t i = 0; i < parts.size() && rc == POST_OK; i++) {
+    const SealPart &p = parts[i];
+    buf.resize((size_t)((p.end - p.first) * SEAL_DIGEST));
+    FILE *f = std::fopen(p.path.c_str(), "rb");
+    if (!f) {
+      vanished = errno == ENOENT;
+      rc = POST_ERR_IO;
+      break;
+    }
+    if (std::fseek(f, (long)SEALP_HEADER, SEEK_SET) != 0 ||
+        std::fread(buf.data(), 1, buf.size(), f) != buf.size() ||
+        std::fwrite(buf.data(), 1, buf.size(), out) != buf.size())
+      rc = POST_ERR_IO;
+    std::fclose(f);
+  }
+  if (rc == POST_OK && (std::fflush(out) != 0 || fsync(fileno(out)) != 0))
+    rc = POST_ERR_IO;
+  std::fclose(out);
+  if (rc == POST_OK && std::rename(tmp.c_str(), sidecar.c_str()) != 0)
+    rc = POST_ERR_IO;
+  if (rc != POST_OK) {
+    (void)::unlink(tmp.c_str());
+    /* a part that went away under us: the shard that finished beside this
+     * one has assembled and is removing them */
+    struct stat st;
+    if (vanished && ::stat(sidecar.c_str(), &st) == 0) {
+      if (pages) *pages = npages;
+      return POST_OK;
+    }
+    set_error("cannot write " + sidecar + " from the part files");
+    return rc;
+  }
+  for (const SealPart &p : parts)
+    if (::unlink(p.path.c_str()) != 0 && errno != ENOENT) {
+      set_error("cannot remove " + p.path);
+      return POST_ERR_IO;
+    }
+  if (pages) *pages = npages;
+  return POST_OK;
+}
+
+int post_seal_assemble(const char *data_dir, uint64_t *pages) {
+  if (!data_dir) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  return seal_assemble(data_dir, pages, false);
+}
+
+int post_seal_digest_stream(const uint8_t *labels, uint64_t count,
+                            uint64_t first_index, const uint64_t *cuts,
+                            uint32_t n_cuts, uint32_t stream_end,
+                            uint32_t provider_id, uint8_t *digests,
+                            uint64_t cap_pages, uint64_t *n_pages) {
+  if (!labels || !digests || !n_pages || count == 0 || (n_cuts && !cuts)) {
+    set_error("null or empty buffer");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (first_index % SEAL_PAGE != 0 || first_index + count < first_index) {
+    set_error("first_index must be a multiple of 1024 and the stream must "
+              "not wrap");
+    return POST_ERR_INVALID_ARGS;
+  }
+  for (uint32_t i = 0; i < n_cuts; i++)
+    if (cuts[i] > count || (i && cuts[i] < cuts[i - 1])) {
+      set_error("cuts must ascend and lie within the buffer");
+      return POST_ERR_INVALID_ARGS;
+    }
+  const uint64_t out_pages = stream_end ? seal_pages(count) : count / SEAL_PAGE;
+  if (cap_pages < out_pages) {
+    set_error("digest buffer holds fewer pages than the labels make");
+    return POST_ERR_INVALID_ARGS;
+  }
+  int rc = require_gpu(provider_id);
+  if (rc != POST_OK) return rc;
+
+  struct Bufs {
+    uint4 *labels = nullptr, *dig = nullptr;
+    SealCarry *carry = nullptr;
+    ~Bufs() {
+      if (labels) (void)hipFree(labels);
+      if (dig) (void)hipFree(dig);
+      if (carry) (void)hipFree(carry);
+    }
+  } d;
+  const uint64_t all_pages = seal_pages(count);
+  HIP_TRY(hipMalloc(&d.labels, (size_t)count * 16));
+  HIP_TRY(hipMalloc(&d.dig, (size_t)(all_pages * SEAL_DIGEST)));
+  HIP_TRY(hipMalloc(&d.carry, 2 * sizeof(SealCarry)));
+  HIP_TRY(hipMemcpy(d.labels, labels, (size_t)count * 16,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d.dig, 0, (size_t)(all_pages * SEAL_DIGEST)));
+  HIP_TRY(hipMemset(d.carry, 0, 2 * sizeof(SealCarry)));
+  uint64_t launches = 0, at = 0;
+  for (uint32_t i = 0; i <= n_cuts; i++) {
+    const uint64_t to = i < n_cuts ? cuts[i] : count;
+    if (to == at) continue;
+    SealStreamArgs a;
+    a.labels = d.labels + at;
+    a.g0 = first_index + at;
+    a.count = to - at;
+    a.stream_end = stream_end ? first_index + count : UINT64_MAX;
+    a.carry_in = d.carry + (launches & 1);
+    a.carry_out = d.carry + ((launches + 1) & 1);
+    /* lane l of the segment is page at / 1024 + l of the buffer */
+    a.digests = d.dig + at / SEAL_PAGE;
+    HIP_TRY(poste_launch_seal_stream_kernel(&a, nullptr));
+    launches++;
+    at = to;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (out_pages)
+    HIP_TRY(hipMemcpy(digests, d.dig, (size_t)(out_pages * SEAL_DIGEST),
+                      hipMemcpyDeviceToHost));
+  *n_pages = out_pages;
   return POST_OK;
 }
 

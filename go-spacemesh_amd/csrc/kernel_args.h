@@ -83,6 +83,37 @@ struct SealKernelArgs {
   uint4 *digests;
 };
 
+/* Seal of a label stream that arrives in segments (init batches, DESIGN
+ * 3.7).  What a page that is still open at the end of a segment hands to
+ * the next one: the SHA-256 chaining value, the labels of the page absorbed
+ * so far (compressed or buffered), and the count % 4 labels not yet
+ * compressed, as they lie in memory. */
+struct SealCarry {
+  uint32_t h[8];
+  uint32_t count;
+  uint32_t pad[3];
+  uint4 buf[3];
+};
+
+/* Segment [g0, g0 + count) of the global label stream, count >= 1, lying at
+ * `labels`; g0 + count <= stream_end (the stream's label count; UINT64_MAX
+ * while the end is not known to lie in this segment).  Lane l works on page
+ * g0 / 1024 + l over [max(1024 p, g0), min(1024 (p + 1), g0 + count)).  The
+ * page open at g0 (g0 % 1024 != 0) starts from *carry_in, every other from
+ * the initial value.  A page that ends inside the segment or at stream_end
+ * gets digests[l]; the last page, when it is still open, leaves *carry_out
+ * and no digest.  digests holds one entry per page the segment touches;
+ * carry_in != carry_out. */
+struct SealStreamArgs {
+  const uint4 *labels;
+  uint64_t g0;
+  uint64_t count;
+  uint64_t stream_end;
+  const SealCarry *carry_in;
+  SealCarry *carry_out;
+  uint4 *digests;
+};
+
 struct VerifyPredArgs {
   const uint4 *labels2;      /* 2 x uint4 per task (full 32-B labels) */
   uint64_t count;
@@ -119,6 +150,11 @@ hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
 /* one lane per page; hipErrorInvalidValue for an empty or unset buffer */
 hipError_t poste_launch_seal_kernel(const SealKernelArgs *args,
                                     hipStream_t stream);
+/* one lane per page the segment touches; hipErrorInvalidValue for an unset
+ * pointer, an empty segment, carry_in == carry_out, or a segment that
+ * wraps or runs past stream_end */
+hipError_t poste_launch_seal_stream_kernel(const SealStreamArgs *args,
+                                           hipStream_t stream);
 uint64_t poste_label_resident_slots(uint32_t gap_shift);
 /* host-only: does the launcher run the lean gap-1 ROMix kernel here? */
 int poste_label_romix_lean_ok(uint32_t scrypt_n, uint32_t gap_shift,

@@ -19,6 +19,10 @@
  *   1024-label page of a chunk the proving pass has on the device, one lane
  *   per page, 64-thread workgroups.
  *
+ * post_seal_stream_kernel: the same digests over a stream that arrives in
+ *   segments of any start and length (init batches); the page
+ *   open at a segment's end is carried to the next launch.
+ *
  * Wave size 64, 256-thread workgroups.  Grid-stride loops size the in-flight
  * label set to the scratch allocation, independent of batch size.
  */
@@ -1293,8 +1297,135 @@ post_seal_kernel(SealKernelArgs a) {
                  __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
 }
 
+__device__ __forceinline__ void seal_msg_label(uint32_t *m, const uint4 l) {
+  m[0] = __builtin_bswap32(l.x);
+  m[1] = __builtin_bswap32(l.y);
+  m[2] = __builtin_bswap32(l.z);
+  m[3] = __builtin_bswap32(l.w);
+}
+
+/* Postdata seal of a stream that arrives in segments: init has
+ * every batch of labels on the device behind the tail kernel, but a batch
+ * neither starts on a page boundary nor holds whole pages.  One lane per
+ * page the segment [g0, g0 + count) touches.  The lane of the page open at
+ * g0 resumes from *carry_in: its message is the r = carry.count % 4 labels
+ * the carry buffers followed by the segment's labels, so its first block is
+ * those r and the first 4 - r labels of the segment; every later block is
+ * four consecutive labels, 16-byte aligned like the buffer itself.  A page
+ * that ends in the segment (or at stream_end) closes as in post_seal_kernel,
+ * with the bit length of the whole page; the last lane, when its page stays
+ * open, writes *carry_out instead.  r is a run-time value: every q[] and m[]
+ * index is a compile-time constant under a predicate, so nothing is indexed
+ * dynamically and nothing goes to scratch. */
+__global__ void __launch_bounds__(POSTE_SEAL_THREADS)
+post_seal_stream_kernel(SealStreamArgs a) {
+  const unsigned long long end = a.g0 + a.count;
+  const unsigned long long p0 = a.g0 / POSTE_SEAL_PAGE_LABELS;
+  const unsigned long long lanes = (end - 1) / POSTE_SEAL_PAGE_LABELS - p0 + 1;
+  const unsigned long long lane =
+      (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= lanes) return;
+  const unsigned long long page_lo = (p0 + lane) * POSTE_SEAL_PAGE_LABELS;
+  const unsigned long long page_hi = page_lo + POSTE_SEAL_PAGE_LABELS;
+  const unsigned long long lo = page_lo > a.g0 ? page_lo : a.g0;
+  const unsigned long long hi = page_hi < end ? page_hi : end;
+  const uint32_t n_seg = (uint32_t)(hi - lo);       /* 1..1024 */
+  const uint32_t before = (uint32_t)(lo - page_lo); /* of the page, earlier */
+  const bool closes = hi == page_hi || hi == a.stream_end;
+  const uint4 *src = a.labels + (lo - a.g0);
+
+  uint32_t h[8], m[16];
+  uint4 buf[3];
+  uint32_t r = 0;
+  if (before) {
+    const uint4 *c = (const uint4 *)a.carry_in;
+    const uint4 h0 = c[0], h1 = c[1];
+    h[0] = h0.x; h[1] = h0.y; h[2] = h0.z; h[3] = h0.w;
+    h[4] = h1.x; h[5] = h1.y; h[6] = h1.z; h[7] = h1.w;
+    r = before % 4;
+#pragma unroll
+    for (int i = 0; i < 3; i++) buf[i] = c[3 + i];
+  } else {
+    sha_init(h);
+#pragma unroll
+    for (int i = 0; i < 3; i++) buf[i] = make_uint4(0, 0, 0, 0);
+  }
+  /* label k of the lane's message is buf[k] for k < r, else src[k - r] */
+  const uint32_t msg = r + n_seg;
+  const uint32_t full = msg / 4, rest = msg % 4;
+
+  uint4 q[4];
+  if (full) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      if ((uint32_t)i < r) {
+        if (i < 3) q[i] = buf[i];
+      } else {
+        q[i] = src[i - r];
+      }
+    }
+  }
+  for (uint32_t b = 0; b < full; b++) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) seal_msg_label(m + 4 * i, q[i]);
+    if (b + 1 < full) {
+      const uint4 *nx = src + (4 * (b + 1) - r);
+#pragma unroll
+      for (int i = 0; i < 4; i++) q[i] = nx[i];
+    }
+    sha_compress(h, m);
+  }
+  /* the rest labels behind the last whole block: still in buf when no block
+   * was compressed, otherwise in memory */
+  uint4 t[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    t[i] = make_uint4(0, 0, 0, 0);
+    if ((uint32_t)i < rest)
+      t[i] = (full == 0 && (uint32_t)i < r) ? buf[i] : src[4 * full + i - r];
+  }
+  if (!closes) {
+    uint4 *c = (uint4 *)a.carry_out;
+    c[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    c[1] = make_uint4(h[4], h[5], h[6], h[7]);
+    c[2] = make_uint4(before + n_seg, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 3; i++) c[3 + i] = t[i];
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; i++) m[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+    if ((uint32_t)i < rest) seal_msg_label(m + 4 * i, t[i]);
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    if ((uint32_t)i == rest) m[4 * i] = 0x80000000u;
+  m[15] = (before + n_seg) * 128; /* bits of the whole page; at most 2^17 */
+  sha_compress(h, m);
+  a.digests[lane] =
+      make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]),
+                 __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
+}
+
 /* host-visible launchers (called from engine.cpp) */
 extern "C" {
+
+hipError_t poste_launch_seal_stream_kernel(const SealStreamArgs *args,
+                                           hipStream_t stream) {
+  if (!args->labels || !args->digests || !args->carry_in ||
+      !args->carry_out || args->carry_in == args->carry_out ||
+      args->count == 0 || args->g0 + args->count < args->g0 ||
+      args->g0 + args->count > args->stream_end)
+    return hipErrorInvalidValue;
+  const uint64_t lanes = (args->g0 + args->count - 1) / POSTE_SEAL_PAGE_LABELS -
+                         args->g0 / POSTE_SEAL_PAGE_LABELS + 1;
+  hipLaunchKernelGGL(
+      post_seal_stream_kernel,
+      dim3((uint32_t)((lanes + POSTE_SEAL_THREADS - 1) / POSTE_SEAL_THREADS)),
+      dim3(POSTE_SEAL_THREADS), 0, stream, *args);
+  return hipGetLastError();
+}
 
 hipError_t poste_launch_seal_kernel(const SealKernelArgs *args,
                                     hipStream_t stream) {

@@ -9,6 +9,9 @@ path imports it — the engine writes, reads and checks the sidecar itself.
     digest         first 16 bytes of SHA-256 over the page's bytes
     sidecar        postdata_seal.bin: 32-byte little-endian header, then
                    ceil(total / 1024) digests
+
+and of the part files a sealed init leaves until they are assembled (§3.7),
+further down.
 """
 import hashlib
 import os
@@ -76,3 +79,60 @@ def read_stream(data_dir: str) -> bytes:
 def sidecar_bytes(data: bytes) -> bytes:
     """What postdata_seal.bin holds for a label stream."""
     return pack_header(len(data) // LABEL_SIZE) + page_digests(data)
+
+
+# Seal during init (DESIGN §3.7): a session over [index_start, index_end)
+# appends its digests to postdata_seal.part-<index_start>:
+#
+#     header  32 bytes little-endian: magic PSTSEALP, page_labels,
+#             digest_bytes, first_page u64, end_page u64 (exclusive)
+#     body    one digest per closed page, in page order
+
+PART_MAGIC = b"PSTSEALP"
+PART_PREFIX = "postdata_seal.part-"
+
+
+def part_name(index_start: int) -> str:
+    return f"{PART_PREFIX}{index_start}"
+
+
+def pack_part_header(first_page: int, end_page: int,
+                     page_labels: int = PAGE_LABELS,
+                     digest_bytes: int = DIGEST_BYTES,
+                     magic: bytes = PART_MAGIC) -> bytes:
+    return HEADER.pack(magic, page_labels, digest_bytes, first_page, end_page)
+
+
+def unpack_part_header(buf: bytes) -> dict:
+    if len(buf) < HEADER_SIZE:
+        raise ValueError("shorter than the header")
+    magic, page_labels, digest_bytes, first, end = HEADER.unpack_from(buf)
+    if magic != PART_MAGIC:
+        raise ValueError("wrong magic")
+    if page_labels != PAGE_LABELS or digest_bytes != DIGEST_BYTES:
+        raise ValueError("unsupported page_labels or digest_bytes")
+    return {"page_labels": page_labels, "digest_bytes": digest_bytes,
+            "first_page": first, "end_page": end}
+
+
+def part_bytes(data: bytes, index_start: int, index_end: int,
+               pages_done=None) -> bytes:
+    """The part file of the shard [index_start, index_end) of the stream
+    `data`, with its first pages_done digests (all by default)."""
+    first = index_start // PAGE_LABELS
+    end = num_pages(index_end)
+    body = page_digests(data[index_start * LABEL_SIZE:
+                             index_end * LABEL_SIZE])
+    if pages_done is not None:
+        body = body[:pages_done * DIGEST_BYTES]
+    return pack_part_header(first, end) + body
+
+
+def stream_digests(data: bytes, cuts=(), stream_end: bool = True) -> bytes:
+    """Digests of a stream that is hashed in segments cut at `cuts`.  Where
+    the cuts fall must not matter, so this is page_digests; without
+    stream_end a ragged last page stays open and has no digest."""
+    total = len(data) // LABEL_SIZE
+    assert all(0 <= c <= total for c in cuts)
+    out = page_digests(data)
+    return out if stream_end else out[:total // PAGE_LABELS * DIGEST_BYTES]

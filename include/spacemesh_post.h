@@ -408,6 +408,59 @@ int post_prove_checked(const char *data_dir, const PostProveConfig *cfg,
                        PostProof *out, uint64_t *bad_pages, uint32_t cap,
                        PostSealReport *r);
 
+/* ---------- seal during init ---------- */
+/* The sidecar of post_seal_data, produced by the init session itself from
+ * the labels as they lie in device memory behind the label kernels (DESIGN.md
+ * 3.7): no second pass over the dir, and the digests witness what the GPU
+ * computed, not what came back from the disk.  Off by default.
+ *
+ * While a session runs, its digests are appended to
+ * postdata_seal.part-<index_start>: a 32-byte little-endian header {magic
+ * "PSTSEALP", u32 page_labels = 1024, u32 digest_bytes = 16, u64 first_page,
+ * u64 end_page (exclusive)}, then one digest per closed page in page order,
+ * each appended after the labels of its page were written.  A new session
+ * over the same range resumes at min(labels on disk rounded down to a page,
+ * 1024 * digests in the part), truncates the part to that and recomputes
+ * from there.  When the session's range is complete the parts are assembled
+ * (post_seal_assemble); with other shards still running that is left to the
+ * last of them.
+ *
+ * Call after post_init_new and before the first post_init_step.  Validated
+ * in this order: POST_ERR_INVALID_ARGS for a NULL session or one without a
+ * data dir; POST_ERR_INVALID_ARGS after the first step; POST_ERR_UNSUPPORTED
+ * for an index_start that is no multiple of 1024 or an index_end that is
+ * neither one nor the end of the label space; POST_ERR_UNSUPPORTED for a
+ * max_file_size that is no multiple of 16; POST_ERR_UNSUPPORTED for a range
+ * that already has labels on disk but neither a part file nor a finished
+ * sidecar; POST_ERR_IO for a part file whose header disagrees with the
+ * session. */
+int post_init_enable_seal(PostInitSession *s);
+
+/* Host-only, no GPU: collect the part files of data_dir, require them to
+ * tile pages [0, ceil(NumUnits * LabelsPerUnit / 1024)) of
+ * postdata_metadata.json with no gap or overlap and every part full, write
+ * postdata_seal.bin (byte for byte what post_seal_data writes for the same
+ * labels) under a temporary name unique to the process, rename it into place
+ * and remove the parts.  *pages (may be NULL) receives the page count.
+ * POST_ERR_IO, with the first missing page range in the message, when the
+ * tiling is incomplete; POST_OK when there is no part and the sidecar is
+ * already there. */
+int post_seal_assemble(const char *data_dir, uint64_t *pages);
+
+/* Test entry beside post_seal_digest_buffer: the labels are the stream
+ * [first_index, first_index + count), first_index a multiple of 1024, cut
+ * into segments at cuts[0 .. n_cuts) (ascending positions within the
+ * buffer; an empty segment is skipped); the stream kernel runs once per
+ * segment with the carry handed on.  With stream_end != 0 the buffer's end
+ * is the end of the stream and a ragged last page is closed: ceil(count /
+ * 1024) digests, otherwise floor.  POST_ERR_INVALID_ARGS when cap_pages is
+ * below that. */
+int post_seal_digest_stream(const uint8_t *labels, uint64_t count,
+                            uint64_t first_index, const uint64_t *cuts,
+                            uint32_t n_cuts, uint32_t stream_end,
+                            uint32_t provider_id, uint8_t *digests,
+                            uint64_t cap_pages, uint64_t *n_pages);
+
 /* ---------- self-healing prove ---------- */
 /* What the seal pass finds bad is put right in the same call (DESIGN.md
  * 3.6): the bad pages are recomputed on the GPU from the identity in

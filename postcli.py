@@ -11,7 +11,7 @@ verification, provider listing and benchmarking
     python postcli.py benchmark [--scrypt-n 8192]
     python postcli.py init --datadir DIR --node-id HEX32 --atx-id HEX32 \
         --num-units U [--labels-per-unit L] [--scrypt-n N] \
-        [--max-file-size B] [--shard R/W]
+        [--max-file-size B] [--shard R/W] [--seal]
     python postcli.py prove --datadir DIR --challenge HEX32 [--nonces 288] \
         [--check-seal [--max-report N] \
          [--heal [--write-back] [--max-heal-pages N]]]
@@ -19,7 +19,7 @@ verification, provider listing and benchmarking
         [--k3 K] [--seed HEX]
     python postcli.py verify-data --datadir DIR [--every K | --fraction PCT] \
         [--seed S] [--shard R/W | --from I --to J] [--max-report N]
-    python postcli.py seal --datadir DIR
+    python postcli.py seal --datadir DIR [--assemble]
     python postcli.py check-seal --datadir DIR [--max-report N]
     python postcli.py repair --datadir DIR [--max-heal-pages N]
 
@@ -37,6 +37,13 @@ pages as label ranges and exits with status 1 when there is one; prove
 --check-seal does the same check during the proving pass itself, prints the
 ranges on stderr as ready verify-data commands, and withholds a proof that
 has an index in a bad page (exit status 1).
+
+init --seal produces the same sidecar during init, from the labels as they
+lie in device memory: each shard appends to
+postdata_seal.part-<index_start> and the last one to finish assembles
+postdata_seal.bin; seal --assemble does that assembly by hand (no GPU) and
+exits with status 2, naming the missing pages, while a shard is unfinished.
+A shard that is not made of whole 1024-label pages is refused (status 2).
 
 prove --check-seal --heal puts the bad pages right in the same call (DESIGN
 §3.6): they are recomputed on the GPU, their hits replaced, and the proof is
@@ -110,8 +117,19 @@ def cmd_init(args):
         data_dir=args.datadir, num_units=args.num_units,
         max_file_size=args.max_file_size, provider_id=args.provider,
         scrypt_n=args.scrypt_n, index_start=start, index_end=end)
+    if args.seal:
+        opts.seal = True
     mgr = gsm_amd.PostSetupManager(node, atx, cfg, opts)
-    mgr.prepare_initializer()
+    if args.seal:
+        # what a sealed session refuses (an unaligned shard, a dir started
+        # without a seal) is the operator's to put right, like a bad sidecar
+        try:
+            mgr.prepare_initializer()
+        except gsm_amd.EngineError as e:
+            print(f"init --seal failed: {e}", file=sys.stderr)
+            return 2
+    else:
+        mgr.prepare_initializer()
     st = mgr.status()
     total = (end or args.num_units * args.labels_per_unit) - start
     print(f"resuming at {st['num_labels_written']}/{total} labels",
@@ -221,6 +239,15 @@ def cmd_prove(args):
 
 def cmd_seal(args):
     t0 = time.time()
+    if args.assemble:
+        try:
+            pages = gsm_amd.seal_assemble(args.datadir)
+        except gsm_amd.EngineError as e:
+            print(f"seal --assemble failed: {e}", file=sys.stderr)
+            return 2
+        print(json.dumps({"pages": pages, "assembled": True,
+                          "seconds": round(time.time() - t0, 2)}))
+        return 0
     try:
         rep = gsm_amd.seal_data(args.datadir, args.provider)
     except gsm_amd.EngineError as e:
@@ -393,6 +420,8 @@ def build_parser():
     i.add_argument("--provider", type=int, default=0)
     i.add_argument("--shard", default=None, help="R/W index-range shard")
     i.add_argument("--pow-difficulty", default=None)
+    i.add_argument("--seal", action="store_true",
+                   help="write postdata_seal.bin from the device during init")
     i.set_defaults(fn=cmd_init)
     p = sub.add_parser("prove")
     p.add_argument("--datadir", required=True)
@@ -413,6 +442,8 @@ def build_parser():
     s = sub.add_parser("seal")
     s.add_argument("--datadir", required=True)
     s.add_argument("--provider", type=int, default=0)
+    s.add_argument("--assemble", action="store_true",
+                   help="no pass: put the part files of init --seal together")
     s.set_defaults(fn=cmd_seal)
     c = sub.add_parser("check-seal")
     c.add_argument("--datadir", required=True)
