@@ -238,6 +238,10 @@ def load_engine() -> ctypes.CDLL:
             "post_selftest_label": (c_int, [ctypes.c_char_p, ctypes.c_char_p,
                                             c_uint64, c_uint32,
                                             ctypes.c_char_p]),
+            "post_selftest_verify_pred": (c_int, [
+                ctypes.c_char_p, c_uint64, ctypes.c_char_p, ctypes.c_char_p,
+                POINTER(c_uint64), c_uint32, POINTER(c_uint32), c_uint32,
+                c_uint32, ctypes.c_char_p]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(lib, name)
@@ -400,6 +404,24 @@ class Engine:
                                           out)
         self._check(rc)
         return out.raw
+
+    def selftest_verify_pred(self, labels: bytes, keys, halves, difficulties,
+                             task_proof, max_blocks: int = 0,
+                             provider_id: int = 0) -> bytes:
+        """Verification's device predicate over caller-made full labels:
+        one pass byte per task.  keys/halves/difficulties are per proof,
+        task_proof maps each 32-byte label to its proof."""
+        count, n = len(labels) // FULL_LABEL_SIZE, len(keys)
+        assert len(labels) == count * FULL_LABEL_SIZE
+        assert len(halves) == n and len(difficulties) == n
+        assert len(task_proof) == count
+        out = ctypes.create_string_buffer(max(count, 1))
+        rc = self.lib.post_selftest_verify_pred(
+            labels, count, b"".join(keys), bytes(halves),
+            (c_uint64 * n)(*difficulties), n,
+            (c_uint32 * count)(*task_proof), max_blocks, provider_id, out)
+        self._check(rc)
+        return out.raw[:count]
 
 
 class PostSetupManager:

@@ -83,6 +83,8 @@ void difficulty_to_be_words(const uint8_t d[32], uint32_t w[8]) {
 }
 
 constexpr uint32_t THREADS = 256;
+/* grid cap of the verification predicate; its loop strides over the rest */
+constexpr uint32_t VERIFY_PRED_MAX_BLOCKS = 8192;
 constexpr uint32_t CAND_CAP = 1 << 16;
 
 /* lookup-gap (kernel_args.h).  Measured on MI355X (gpurun summary3-5
@@ -3675,6 +3677,12 @@ int post_verify_batch_seeded(const PostProof *proofs,
   std::vector<uint32_t> commit_words((size_t)n * 8);
   std::vector<std::vector<uint64_t>> proof_indices(n);
   std::vector<std::vector<Task>> per_proof_tasks(n);
+  /* position of a proof's first out-of-range index among the positions
+   * checked, UINT32_MAX for none.  The verdict walks the positions in
+   * order and stops at the first failure of either kind (an index out of
+   * range, a label above the difficulty), so this one holds only if no
+   * task before it fails on the device. */
+  std::vector<uint32_t> oor_position(n, UINT32_MAX);
 
   /* per-proof host prep (commitment blake3, pow verify, index unpack,
    * subset sampling) is independent across proofs and dominates the
@@ -3732,9 +3740,8 @@ int post_verify_batch_seeded(const PostProof *proofs,
         return;
       }
       uint64_t li = proof_indices[p][pos];
-      if (li >= num_labels) {
-        statuses[p] = POST_ERR_INVALID_INDEX;
-        if (invalid_indices) invalid_indices[p] = pos;
+      if (li >= num_labels) { /* later positions cannot decide */
+        oor_position[p] = pos;
         return;
       }
       per_proof_tasks[p].push_back({li, p, pos});
@@ -3767,7 +3774,17 @@ int post_verify_batch_seeded(const PostProof *proofs,
     tasks.insert(tasks.end(), per_proof_tasks[p].begin(),
                  per_proof_tasks[p].end());
   }
-  if (tasks.empty()) return POST_OK;
+  auto apply_out_of_range = [&] {
+    for (uint32_t p = 0; p < n; p++) {
+      if (statuses[p] != POST_OK || oor_position[p] == UINT32_MAX) continue;
+      statuses[p] = POST_ERR_INVALID_INDEX;
+      if (invalid_indices) invalid_indices[p] = oor_position[p];
+    }
+  };
+  if (tasks.empty()) {
+    apply_out_of_range();
+    return POST_OK;
+  }
 
   /* scratch-bounded chunks of label recomputes on the GPU */
   size_t free_b = 0, total_b = 0;
@@ -3890,7 +3907,7 @@ int post_verify_batch_seeded(const PostProof *proofs,
     pa.difficulty = ws->d_vdiff;
     pa.pass = ws->d_pass;
     uint32_t pblocks = (uint32_t)std::min<uint64_t>(
-        (tasks.size() + THREADS - 1) / THREADS, 8192);
+        (tasks.size() + THREADS - 1) / THREADS, VERIFY_PRED_MAX_BLOCKS);
     HIP_TRY(poste_launch_verify_pred_kernel(&pa, pblocks, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     if (dbg) {
@@ -3910,6 +3927,7 @@ int post_verify_batch_seeded(const PostProof *proofs,
       if (invalid_indices) invalid_indices[t.proof] = t.position;
     }
   }
+  apply_out_of_range();
   return POST_OK;
 }
 
@@ -3989,6 +4007,74 @@ int post_selftest_label(const uint8_t node_id[32],
   uint8_t cm[32];
   poste::commitment(node_id, commitment_atx_id, cm);
   return poste::host_label(cm, index, scrypt_n, out);
+}
+
+int post_selftest_verify_pred(const uint8_t *labels, uint64_t count,
+                              const uint8_t *keys, const uint8_t *halves,
+                              const uint64_t *difficulties, uint32_t n_proofs,
+                              const uint32_t *task_proof, uint32_t max_blocks,
+                              uint32_t provider_id, uint8_t *pass) {
+  if (!labels || !keys || !halves || !difficulties || !task_proof || !pass ||
+      count == 0 || n_proofs == 0)
+    return POST_ERR_INVALID_ARGS;
+  for (uint64_t i = 0; i < count; i++)
+    if (task_proof[i] >= n_proofs) {
+      set_error("task_proof entry out of range");
+      return POST_ERR_INVALID_ARGS;
+    }
+  int rc = require_gpu(provider_id);
+  if (rc != POST_OK) return rc;
+
+  std::vector<uint32_t> rk((size_t)n_proofs * 44);
+  for (uint32_t p = 0; p < n_proofs; p++)
+    poste::aes128_expand(keys + (size_t)p * 16, rk.data() + (size_t)p * 44);
+  DeviceTables tbl;
+  rc = get_aes_tables((int)provider_id, tbl);
+  if (rc != POST_OK) return rc;
+
+  struct Bufs {
+    uint8_t *labels = nullptr, *half = nullptr, *pass = nullptr;
+    uint32_t *rk = nullptr, *task_proof = nullptr;
+    uint64_t *diff = nullptr;
+    ~Bufs() {
+      (void)hipFree(labels); (void)hipFree(half); (void)hipFree(pass);
+      (void)hipFree(rk); (void)hipFree(task_proof); (void)hipFree(diff);
+    }
+  } d;
+  HIP_TRY(hipMalloc(&d.labels, (size_t)count * 32));
+  HIP_TRY(hipMalloc(&d.task_proof, (size_t)count * 4));
+  HIP_TRY(hipMalloc(&d.pass, (size_t)count));
+  HIP_TRY(hipMalloc(&d.rk, rk.size() * 4));
+  HIP_TRY(hipMalloc(&d.half, n_proofs));
+  HIP_TRY(hipMalloc(&d.diff, (size_t)n_proofs * 8));
+  HIP_TRY(hipMemcpy(d.labels, labels, (size_t)count * 32,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.task_proof, task_proof, (size_t)count * 4,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d.pass, 0xEE, (size_t)count)); /* neither verdict */
+  HIP_TRY(hipMemcpy(d.rk, rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.half, halves, n_proofs, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.diff, difficulties, (size_t)n_proofs * 8,
+                    hipMemcpyHostToDevice));
+
+  VerifyPredArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.labels2 = (const uint4 *)d.labels;
+  pa.count = count;
+  pa.te = tbl.d_te;
+  pa.sbox = tbl.d_sbox;
+  pa.rk = d.rk;
+  pa.task_proof = d.task_proof;
+  pa.half = d.half;
+  pa.difficulty = d.diff;
+  pa.pass = d.pass;
+  uint32_t pblocks = (uint32_t)std::min<uint64_t>(
+      (count + THREADS - 1) / THREADS,
+      max_blocks ? max_blocks : VERIFY_PRED_MAX_BLOCKS);
+  HIP_TRY(poste_launch_verify_pred_kernel(&pa, pblocks, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(pass, d.pass, (size_t)count, hipMemcpyDeviceToHost));
+  return POST_OK;
 }
 
 } /* extern "C" */

@@ -244,7 +244,10 @@ int post_verify(const PostProof *proof, const PostProofMetadata *meta,
 /* Batched verification (the verifier-pool steady state, BASELINE config 5):
  * n proofs with per-proof metadata; statuses[i] and invalid_indices[i]
  * receive per-proof results.  One kernel launch recomputes all sampled
- * labels and one applies the AES threshold predicate. */
+ * labels and one applies the AES threshold predicate.  invalid_indices[i]
+ * is the first position, in the order the positions are checked (0..k2-1,
+ * or the subset's sampling order), that fails either way: its index is out
+ * of range, or its label is not below the difficulty. */
 int post_verify_batch(const PostProof *proofs, const PostProofMetadata *metas,
                       uint32_t n, const PostVerifyConfig *cfg,
                       int *statuses, uint32_t *invalid_indices);
@@ -543,6 +546,20 @@ void post_selftest_aes128(const uint8_t key[16], const uint8_t in[16],
 int post_selftest_label(const uint8_t node_id[32],
                         const uint8_t commitment_atx_id[32], uint64_t index,
                         uint32_t scrypt_n, uint8_t out[32]);
+/* Verification's device predicate on labels the caller supplies (used only
+ * by tests): `count` full 32-byte labels, `n_proofs` 16-byte AES keys, half
+ * bytes (0/1) and u64 difficulties, and `count` task->proof indices, each
+ * below n_proofs (POST_ERR_INVALID_ARGS otherwise).  The keys are expanded
+ * by the engine's host AES and the production kernel is launched by the
+ * production launcher over the device tables verification uses, with
+ * min(ceil(count / 256), max_blocks) blocks; max_blocks == 0 is the
+ * production cap (8192).  pass[i] is 1 where task i's selected little-endian
+ * u64 of AES(key, label[0..16)) is below its proof's difficulty, else 0. */
+int post_selftest_verify_pred(const uint8_t *labels, uint64_t count,
+                              const uint8_t *keys, const uint8_t *halves,
+                              const uint64_t *difficulties, uint32_t n_proofs,
+                              const uint32_t *task_proof, uint32_t max_blocks,
+                              uint32_t provider_id, uint8_t *pass);
 
 /* version / build info string */
 const char *post_engine_version(void);

@@ -29,6 +29,7 @@ def test_all_header_symbols_exported():
     names = re.findall(r"^\s*(?:const char \*|int|void|uint64_t)\s+"
                        r"(post_\w+)\s*\(", src, re.M)
     assert len(names) >= 18, names
+    assert "post_selftest_verify_pred" in names
     for n in names:
         assert hasattr(lib, n), f"symbol {n} missing from libpost_hip.so"
 

@@ -185,12 +185,13 @@ def test_gpu_verify_verdicts_match_oracle(roundtrip):
         return op
 
     # corrupt each byte of the indices in turn; engine and oracle must agree
-    agree = 0
     for pos in range(len(proof.indices)):
         bad = bytearray(proof.indices)
         bad[pos] ^= 0x5A
         bp = gsm_amd.PostProof(proof.nonce, bytes(bad), proof.pow)
-        orc, _ = o.verify(o_proof(bp), ometa, N, 12, 8, 8, None, -1, POW_DIFF)
+        orc, oinv = o.verify(o_proof(bp), ometa, N, 12, 8, 8, None, -1,
+                             POW_DIFF)
+        einv = None
         try:
             ver.verify(bp, meta)
             erc = 0
@@ -198,10 +199,11 @@ def test_gpu_verify_verdicts_match_oracle(roundtrip):
             erc = {gsm_amd.api.Status.INVALID_INDEX: 1,
                    gsm_amd.api.Status.POW: 2,
                    gsm_amd.api.Status.INVALID_ARGS: 3}.get(e.code, -1)
-        assert (orc == 0) == (erc == 0), (pos, orc, erc)
-        if orc == erc:
-            agree += 1
-    assert agree >= len(proof.indices) - 1  # allow err-code drift, not verdict
+            if erc == 1:  # "... invalid POST index at position <n>"
+                einv = int(str(e).rsplit(" ", 1)[1])
+        assert orc == erc, (pos, orc, erc)
+        if orc == 1:
+            assert einv == oinv, (pos, einv, oinv)
 
     # bad pow
     bp = gsm_amd.PostProof(proof.nonce, proof.indices, proof.pow + 1)
