@@ -171,30 +171,6 @@ __device__ __forceinline__ void blockmix_z(uint32_t X0[4], uint32_t X1[4]) {
   X1[0] = t0; X1[1] = t1; X1[2] = t2; X1[3] = t3;
 }
 
-/* canonical(16 words) -> this lane's z elements for one 64-B block */
-__device__ __forceinline__ void canon_to_z(const uint32_t x[16], uint32_t sub,
-                                           uint32_t z[4]) {
-  /* z_v[l] = x[(4v + 5l) % 16] */
-  uint32_t s0 = sub == 0 ? x[0] : sub == 1 ? x[5] : sub == 2 ? x[10] : x[15];
-  uint32_t s1 = sub == 0 ? x[4] : sub == 1 ? x[9] : sub == 2 ? x[14] : x[3];
-  uint32_t s2 = sub == 0 ? x[8] : sub == 1 ? x[13] : sub == 2 ? x[2] : x[7];
-  uint32_t s3 = sub == 0 ? x[12] : sub == 1 ? x[1] : sub == 2 ? x[6] : x[11];
-  z[0] = s0; z[1] = s1; z[2] = s2; z[3] = s3;
-}
-
-/* this quad's z vectors -> big-endian SHA message words of the canonical
- * 64-B block (fused broadcast+byteswap, no staging buffers) */
-__device__ __forceinline__ void z_to_msg_be(const uint32_t z[4],
-                                            uint32_t m[16]) {
-#pragma unroll
-  for (int v = 0; v < 4; v++) {
-    m[(4 * v + 0) & 15] = __builtin_bswap32(SWZ(z[v], 0x00));
-    m[(4 * v + 5) & 15] = __builtin_bswap32(SWZ(z[v], 0x55));
-    m[(4 * v + 10) & 15] = __builtin_bswap32(SWZ(z[v], 0xAA));
-    m[(4 * v + 15) & 15] = __builtin_bswap32(SWZ(z[v], 0xFF));
-  }
-}
-
 /* ------------------------- label kernel ------------------------- */
 /* LabelKernelArgs: see kernel_args.h */
 
@@ -246,21 +222,47 @@ __device__ __forceinline__ void hmac_states_for(const uint32_t *cw,
   sha_compress(ho, m);
 }
 
-/* prologue: PBKDF2(P, "", 1, 128) -> xbuf in quad-z layout.  Every lane of
- * a quad computes the same SHA chain (redundant, ~0.1% of the ROMix cost)
- * and keeps only its own z slice. */
+/* The SHA kernels (prologue, tail, audit tail) run ONE lane per label, so a
+ * compression is computed once; only ROMix works in quads.  xbuf keeps the
+ * quad-z layout ROMix reads: of a task's eight uint4, chunk c is what quad
+ * lane c holds of block 0, (z0[c], z1[c], z2[c], z3[c]) with
+ * z_v[l] = x[(4v + 5l) % 16], and chunk 4 + c the same of block 1.  A lane
+ * here reads or writes all eight, the permutation resolved at compile
+ * time. */
+
+/* canonical 16 words of one 64-B block -> its four chunks */
+__device__ __forceinline__ void canon_to_chunks(const uint32_t x[16],
+                                                uint4 *p) {
+#pragma unroll
+  for (int c = 0; c < 4; c++)
+    p[c] = make_uint4(x[(5 * c) & 15], x[(4 + 5 * c) & 15],
+                      x[(8 + 5 * c) & 15], x[(12 + 5 * c) & 15]);
+}
+
+/* four chunks of one block -> big-endian SHA message words of the canonical
+ * 64-B block */
+__device__ __forceinline__ void chunks_to_msg_be(const uint4 *p,
+                                                 uint32_t m[16]) {
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    const uint4 v = p[c];
+    m[(5 * c) & 15] = __builtin_bswap32(v.x);
+    m[(4 + 5 * c) & 15] = __builtin_bswap32(v.y);
+    m[(8 + 5 * c) & 15] = __builtin_bswap32(v.z);
+    m[(12 + 5 * c) & 15] = __builtin_bswap32(v.w);
+  }
+}
+
+/* prologue: PBKDF2(P, "", 1, 128) -> xbuf in quad-z layout */
 __global__ void __launch_bounds__(POSTE_THREADS)
 post_label_prologue_kernel(LabelKernelArgs a) {
   const unsigned long long lane =
       (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long group = lane >> 2;
   const unsigned long long gstride =
-      ((unsigned long long)gridDim.x * blockDim.x) >> 2;
-  const uint32_t sub = (uint32_t)(lane & 3);
+      (unsigned long long)gridDim.x * blockDim.x;
   uint4 *X = (uint4 *)a.xbuf;
 
-  for (unsigned long long task = group; task < a.count;
-       task += gstride) {
+  for (unsigned long long task = lane; task < a.count; task += gstride) {
     const unsigned long long index = a.indices ? a.indices[task]
                                                : a.start + task;
     const uint32_t *cw = a.commit_ids
@@ -268,7 +270,7 @@ post_label_prologue_kernel(LabelKernelArgs a) {
                              : a.commitment_le;
     uint32_t hi[8], ho[8], m[16];
     hmac_states_for(cw, index, hi, ho);
-    uint32_t Z0[4], Z1[4];
+    uint4 *p = X + task * 8ull;
     for (uint32_t half = 0; half < 2; half++) {
       uint32_t cblk[16];
 #pragma unroll
@@ -289,11 +291,8 @@ post_label_prologue_kernel(LabelKernelArgs a) {
         for (int k = 0; k < 8; k++)
           cblk[8 * q + k] = __builtin_bswap32(d[k]);
       }
-      canon_to_z(cblk, sub, half == 0 ? Z0 : Z1);
+      canon_to_chunks(cblk, p + 4 * half);
     }
-    uint4 *p = X + task * 8ull;
-    p[sub] = make_uint4(Z0[0], Z0[1], Z0[2], Z0[3]);
-    p[sub + 4] = make_uint4(Z1[0], Z1[1], Z1[2], Z1[3]);
   }
 }
 
@@ -531,18 +530,15 @@ __global__ void __launch_bounds__(POSTE_THREADS)
 post_label_tail_kernel(LabelKernelArgs a) {
   const unsigned long long lane =
       (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long group = lane >> 2;
   const unsigned long long gstride =
-      ((unsigned long long)gridDim.x * blockDim.x) >> 2;
-  const uint32_t sub = (uint32_t)(lane & 3);
+      (unsigned long long)gridDim.x * blockDim.x;
   uint4 *X = (uint4 *)a.xbuf;
 
   uint32_t min_lab[8];
   unsigned long long min_idx = 0;
   int min_found = 0;
 
-  for (unsigned long long task = group; task < a.count;
-       task += gstride) {
+  for (unsigned long long task = lane; task < a.count; task += gstride) {
     const unsigned long long index = a.indices ? a.indices[task]
                                                : a.start + task;
     const uint32_t *cw = a.commit_ids
@@ -550,19 +546,13 @@ post_label_tail_kernel(LabelKernelArgs a) {
                              : a.commitment_le;
     uint32_t hi[8], ho[8], m[16];
     hmac_states_for(cw, index, hi, ho);
-    uint32_t Z0[4], Z1[4];
-    {
-      uint4 *p = X + task * 8ull;
-      uint4 v0 = p[sub], v1 = p[sub + 4];
-      Z0[0] = v0.x; Z0[1] = v0.y; Z0[2] = v0.z; Z0[3] = v0.w;
-      Z1[0] = v1.x; Z1[1] = v1.y; Z1[2] = v1.z; Z1[3] = v1.w;
-    }
+    const uint4 *p = X + task * 8ull;
     uint32_t h[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) h[i] = hi[i];
-    z_to_msg_be(Z0, m);
+    chunks_to_msg_be(p, m);
     sha_compress(h, m);
-    z_to_msg_be(Z1, m);
+    chunks_to_msg_be(p + 4, m);
     sha_compress(h, m);
     m[0] = 1;
     m[1] = 0x80000000u;
@@ -573,7 +563,7 @@ post_label_tail_kernel(LabelKernelArgs a) {
     uint32_t lab_be[8]; /* full label as big-endian words */
     hmac_outer(ho, h, lab_be);
 
-    if (a.out && sub == 0) {
+    if (a.out) {
       if (a.out_full) {
         uint4 *o = (uint4 *)(a.out + task * 32ull);
         o[0] = make_uint4(__builtin_bswap32(lab_be[0]),
@@ -593,7 +583,7 @@ post_label_tail_kernel(LabelKernelArgs a) {
       }
     }
 
-    if (a.has_difficulty && sub == 0) {
+    if (a.has_difficulty) {
       /* lexicographic byte compare == numeric compare of BE word sequence */
       bool below_diff = false, below_min = false;
 #pragma unroll
@@ -676,14 +666,11 @@ post_label_audit_tail_kernel(AuditKernelArgs aa) {
   const LabelKernelArgs &a = aa.label;
   const unsigned long long lane =
       (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long group = lane >> 2;
   const unsigned long long gstride =
-      ((unsigned long long)gridDim.x * blockDim.x) >> 2;
-  const uint32_t sub = (uint32_t)(lane & 3);
+      (unsigned long long)gridDim.x * blockDim.x;
   const uint4 *X = (const uint4 *)a.xbuf;
 
-  for (unsigned long long task = group; task < a.count;
-       task += gstride) {
+  for (unsigned long long task = lane; task < a.count; task += gstride) {
     const unsigned long long index = a.indices ? a.indices[task]
                                                : a.start + task;
     const uint32_t *cw = a.commit_ids
@@ -691,19 +678,13 @@ post_label_audit_tail_kernel(AuditKernelArgs aa) {
                              : a.commitment_le;
     uint32_t hi[8], ho[8], m[16];
     hmac_states_for(cw, index, hi, ho);
-    uint32_t Z0[4], Z1[4];
-    {
-      const uint4 *p = X + task * 8ull;
-      uint4 v0 = p[sub], v1 = p[sub + 4];
-      Z0[0] = v0.x; Z0[1] = v0.y; Z0[2] = v0.z; Z0[3] = v0.w;
-      Z1[0] = v1.x; Z1[1] = v1.y; Z1[2] = v1.z; Z1[3] = v1.w;
-    }
+    const uint4 *p = X + task * 8ull;
     uint32_t h[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) h[i] = hi[i];
-    z_to_msg_be(Z0, m);
+    chunks_to_msg_be(p, m);
     sha_compress(h, m);
-    z_to_msg_be(Z1, m);
+    chunks_to_msg_be(p + 4, m);
     sha_compress(h, m);
     m[0] = 1;
     m[1] = 0x80000000u;
@@ -714,7 +695,7 @@ post_label_audit_tail_kernel(AuditKernelArgs aa) {
     uint32_t lab_be[8];
     hmac_outer(ho, h, lab_be);
 
-    if (sub == 0) {
+    {
       const uint4 want = aa.expected[task];
       const uint4 got = make_uint4(__builtin_bswap32(lab_be[0]),
                                    __builtin_bswap32(lab_be[1]),
@@ -1456,14 +1437,26 @@ int poste_label_romix_lean_ok(uint32_t scrypt_n, uint32_t gap_shift,
          (uint64_t)scrypt_n * scratch_lanes < (1ull << 32);
 }
 
+/* Grid of a SHA kernel (prologue, tail, audit tail): one lane per label, so
+ * one workgroup per POSTE_THREADS labels, and never more workgroups than
+ * the caller's `blocks`, which counts 64-quad ROMix workgroups.  The tail
+ * appends at most one candidate per workgroup, so the callers' bounds on
+ * candidates per launch, taken from `blocks`, hold as before. */
+static uint32_t sha_blocks(const LabelKernelArgs *args, uint32_t blocks) {
+  const uint64_t need = (args->count + POSTE_THREADS - 1) / POSTE_THREADS;
+  const uint64_t g = need < blocks ? need : blocks;
+  return g ? (uint32_t)g : 1u;
+}
+
 /* prologue + ROMix, the part every label pipeline shares */
 static void launch_label_prologue_romix(const LabelKernelArgs *args,
                                         uint32_t blocks, hipStream_t stream) {
   /* Two labels per quad (a dual-stream form of the lean kernel, spill-free
    * at 58 VGPRs) measured 4% slower than one label per quad and was
    * removed: profiles/r03_kernel_stats.md. */
-  hipLaunchKernelGGL(post_label_prologue_kernel, dim3(blocks),
-                     dim3(POSTE_THREADS), 0, stream, *args);
+  hipLaunchKernelGGL(post_label_prologue_kernel,
+                     dim3(sha_blocks(args, blocks)), dim3(POSTE_THREADS), 0,
+                     stream, *args);
   if (poste_label_romix_lean_ok(args->scrypt_n, args->gap_shift,
                                 args->scratch_lanes)) {
     hipLaunchKernelGGL(post_label_romix_kernel, dim3(blocks),
@@ -1477,21 +1470,22 @@ static void launch_label_prologue_romix(const LabelKernelArgs *args,
 hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
                                      uint32_t blocks, hipStream_t stream) {
   launch_label_prologue_romix(args, blocks, stream);
-  hipLaunchKernelGGL(post_label_tail_kernel, dim3(blocks),
+  hipLaunchKernelGGL(post_label_tail_kernel, dim3(sha_blocks(args, blocks)),
                      dim3(POSTE_THREADS), 0, stream, *args);
   return hipGetLastError();
 }
 
 hipError_t poste_launch_label_prologue(const LabelKernelArgs *args,
                                        uint32_t blocks, hipStream_t stream) {
-  hipLaunchKernelGGL(post_label_prologue_kernel, dim3(blocks),
-                     dim3(POSTE_THREADS), 0, stream, *args);
+  hipLaunchKernelGGL(post_label_prologue_kernel,
+                     dim3(sha_blocks(args, blocks)), dim3(POSTE_THREADS), 0,
+                     stream, *args);
   return hipGetLastError();
 }
 
 hipError_t poste_launch_label_tail(const LabelKernelArgs *args,
                                    uint32_t blocks, hipStream_t stream) {
-  hipLaunchKernelGGL(post_label_tail_kernel, dim3(blocks),
+  hipLaunchKernelGGL(post_label_tail_kernel, dim3(sha_blocks(args, blocks)),
                      dim3(POSTE_THREADS), 0, stream, *args);
   return hipGetLastError();
 }
@@ -1528,7 +1522,8 @@ hipError_t poste_launch_romix_mix(const RomixPhaseArgs *args,
 hipError_t poste_launch_label_audit(const AuditKernelArgs *args,
                                     uint32_t blocks, hipStream_t stream) {
   launch_label_prologue_romix(&args->label, blocks, stream);
-  hipLaunchKernelGGL(post_label_audit_tail_kernel, dim3(blocks),
+  hipLaunchKernelGGL(post_label_audit_tail_kernel,
+                     dim3(sha_blocks(&args->label, blocks)),
                      dim3(POSTE_THREADS), 0, stream, *args);
   return hipGetLastError();
 }
