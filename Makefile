@@ -12,7 +12,8 @@ all: $(ENGINE) oracle
 
 SRCS_ENGINE := $(CSRC)/kernels.hip $(CSRC)/engine.cpp $(CSRC)/crypto_host.cpp
 HDRS_ENGINE := $(CSRC)/post_common.h $(CSRC)/kernel_args.h \
-               $(CSRC)/crypto_host.h include/spacemesh_post.h
+               $(CSRC)/crypto_host.h $(CSRC)/hip_owned.h \
+               include/spacemesh_post.h
 
 $(ENGINE): $(SRCS_ENGINE) $(HDRS_ENGINE)
 	$(HIPCC) $(HIPFLAGS) -shared $(SRCS_ENGINE) -o $@
@@ -36,11 +37,21 @@ go-spacemesh_amd/libpost_hip_scan1.so: $(SRCS_ENGINE) $(HDRS_ENGINE)
 scan1: go-spacemesh_amd/libpost_hip_scan1.so
 .PHONY: scan1
 
+# Host check of the owning handles (csrc/hip_owned.h) under ASan + UBSan: a
+# stand-alone program, needs no GPU (without one every creating call fails,
+# which is the path that must not double-free).  Not part of `all`.
+tools/hip_owned_test: tools/hip_owned_test.cpp $(CSRC)/hip_owned.h
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -Wall \
+	    -Xarch_host -fsanitize=address,undefined $< -o $@
+hip_owned_test: tools/hip_owned_test
+	./tools/hip_owned_test
+.PHONY: hip_owned_test
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(ENGINE)
+	rm -f $(ENGINE) tools/hip_owned_test
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -32,14 +32,21 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include "crypto_host.h"
+#include "hip_owned.h"
 #include "kernel_args.h"
 #include "post_common.h"
 
 namespace {
+
+using hip_owned::DevBuf;
+using hip_owned::Event;
+using hip_owned::PinnedBuf;
+using hip_owned::Stream;
 
 thread_local std::string g_last_error;
 
@@ -120,20 +127,20 @@ uint64_t prove_chunk_labels() {
  * safe for concurrent workers; they serialize on the device section. */
 struct VerifyWorkspace {
   std::mutex mu;
-  uint32_t *d_scratch = nullptr;
+  DevBuf<uint32_t> d_scratch;
   size_t scratch_cap = 0; /* bytes */
-  uint64_t *d_idx = nullptr;
-  uint32_t *d_cid = nullptr;
-  uint8_t *d_out = nullptr;
-  uint32_t *d_xbuf = nullptr;
+  DevBuf<uint64_t> d_idx;
+  DevBuf<uint32_t> d_cid;
+  DevBuf<uint8_t> d_out;
+  DevBuf<uint32_t> d_xbuf;
   size_t tasks_cap = 0;
-  uint32_t *d_cm = nullptr;
+  DevBuf<uint32_t> d_cm;
   size_t cm_cap = 0; /* words */
-  uint32_t *d_vrk = nullptr; /* 44 words per proof */
-  uint8_t *d_half = nullptr;
-  uint64_t *d_vdiff = nullptr;
+  DevBuf<uint32_t> d_vrk; /* 44 words per proof */
+  DevBuf<uint8_t> d_half;
+  DevBuf<uint64_t> d_vdiff;
   size_t proofs_cap = 0;
-  uint8_t *d_pass = nullptr; /* per task, with tasks_cap */
+  DevBuf<uint8_t> d_pass; /* per task, with tasks_cap */
 };
 std::mutex g_vws_mu;
 std::map<int, VerifyWorkspace *> g_vws;
@@ -147,17 +154,15 @@ VerifyWorkspace *get_verify_ws(int dev) {
   return w;
 }
 
+/* growing a group releases all of it first, then allocates */
 int ws_reserve_proofs(VerifyWorkspace *w, size_t proofs) {
   if (proofs > w->proofs_cap) {
     size_t cap = std::max<size_t>(proofs, 1024);
-    if (w->d_vrk) (void)hipFree(w->d_vrk);
-    if (w->d_half) (void)hipFree(w->d_half);
-    if (w->d_vdiff) (void)hipFree(w->d_vdiff);
-    w->d_vrk = nullptr; w->d_half = nullptr; w->d_vdiff = nullptr;
+    w->d_vrk.reset(); w->d_half.reset(); w->d_vdiff.reset();
     w->proofs_cap = 0;
-    HIP_TRY(hipMalloc(&w->d_vrk, cap * 44 * 4));
-    HIP_TRY(hipMalloc(&w->d_half, cap));
-    HIP_TRY(hipMalloc(&w->d_vdiff, cap * 8));
+    HIP_TRY(w->d_vrk.alloc(cap * 44 * 4));
+    HIP_TRY(w->d_half.alloc(cap));
+    HIP_TRY(w->d_vdiff.alloc(cap * 8));
     w->proofs_cap = cap;
   }
   return POST_OK;
@@ -166,41 +171,32 @@ int ws_reserve_proofs(VerifyWorkspace *w, size_t proofs) {
 int ws_reserve(VerifyWorkspace *w, size_t scratch_bytes, size_t tasks,
                size_t cm_words) {
   if (scratch_bytes > w->scratch_cap) {
-    if (w->d_scratch) (void)hipFree(w->d_scratch);
-    w->d_scratch = nullptr;
     w->scratch_cap = 0;
-    HIP_TRY(hipMalloc(&w->d_scratch, scratch_bytes));
+    HIP_TRY(w->d_scratch.alloc(scratch_bytes));
     w->scratch_cap = scratch_bytes;
   }
   if (tasks > w->tasks_cap) {
     size_t cap = std::max<size_t>(tasks, 4096);
-    if (w->d_idx) (void)hipFree(w->d_idx);
-    if (w->d_cid) (void)hipFree(w->d_cid);
-    if (w->d_out) (void)hipFree(w->d_out);
-    if (w->d_xbuf) (void)hipFree(w->d_xbuf);
-    if (w->d_pass) (void)hipFree(w->d_pass);
-    w->d_idx = nullptr; w->d_cid = nullptr; w->d_out = nullptr;
-    w->d_xbuf = nullptr; w->d_pass = nullptr;
+    w->d_idx.reset(); w->d_cid.reset(); w->d_out.reset();
+    w->d_xbuf.reset(); w->d_pass.reset();
     w->tasks_cap = 0;
-    HIP_TRY(hipMalloc(&w->d_idx, cap * 8));
-    HIP_TRY(hipMalloc(&w->d_cid, cap * 4));
-    HIP_TRY(hipMalloc(&w->d_out, cap * 32));
-    HIP_TRY(hipMalloc(&w->d_xbuf, cap * 128));
-    HIP_TRY(hipMalloc(&w->d_pass, cap));
+    HIP_TRY(w->d_idx.alloc(cap * 8));
+    HIP_TRY(w->d_cid.alloc(cap * 4));
+    HIP_TRY(w->d_out.alloc(cap * 32));
+    HIP_TRY(w->d_xbuf.alloc(cap * 128));
+    HIP_TRY(w->d_pass.alloc(cap));
     w->tasks_cap = cap;
   }
   if (cm_words > w->cm_cap) {
     size_t cap = std::max<size_t>(cm_words, 1024);
-    if (w->d_cm) (void)hipFree(w->d_cm);
-    w->d_cm = nullptr;
     w->cm_cap = 0;
-    HIP_TRY(hipMalloc(&w->d_cm, cap * 4));
+    HIP_TRY(w->d_cm.alloc(cap * 4));
     w->cm_cap = cap;
   }
   return POST_OK;
 }
 
-struct DeviceTables { /* AES tables resident per device */
+struct DeviceTables { /* AES tables, resident per device for good */
   uint32_t *d_te = nullptr;
   uint8_t *d_sbox = nullptr;
 };
@@ -217,11 +213,17 @@ int get_aes_tables(int dev, DeviceTables &out) {
   static uint32_t te[1024];
   static uint8_t sbox[256];
   poste::aes128_tables(te, sbox);
+  DevBuf<uint32_t> d_te;
+  DevBuf<uint8_t> d_sbox;
+  HIP_TRY(d_te.alloc(sizeof(te)));
+  HIP_TRY(d_sbox.alloc(sizeof(sbox)));
+  HIP_TRY(hipMemcpy(d_te.get(), te, sizeof(te), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_sbox.get(), sbox, sizeof(sbox), hipMemcpyHostToDevice));
   DeviceTables t;
-  HIP_TRY(hipMalloc(&t.d_te, sizeof(te)));
-  HIP_TRY(hipMalloc(&t.d_sbox, sizeof(sbox)));
-  HIP_TRY(hipMemcpy(t.d_te, te, sizeof(te), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t.d_sbox, sbox, sizeof(sbox), hipMemcpyHostToDevice));
+  t.d_te = d_te.get();
+  t.d_sbox = d_sbox.get();
+  (void)d_te.release();
+  (void)d_sbox.release();
   g_tables[dev] = t;
   out = t;
   return POST_OK;
@@ -259,6 +261,28 @@ int post_providers(PostProvider *providers, uint32_t cap, uint32_t *count) {
 
 /* ------------------------- init session ------------------------- */
 
+/* What one batch leaves for the host.  The monolithic path uses set 0 alone
+ * (and fetches its candidates through pageable memory); the split path
+ * alternates between the two, so batch i is processed while batch i+1 runs.
+ * Set 1 exists only on the split path, and its d_out only when the labels
+ * are not kept on the device. */
+struct OutputSet {
+  DevBuf<uint8_t> d_out;     /* batch output (16 B per label) */
+  PinnedBuf<uint8_t> h_batch;
+  DevBuf<PostVrfCandidate> d_cand;
+  DevBuf<unsigned int> d_cand_count;
+  /* split path only */
+  PinnedBuf<PostVrfCandidate> h_cand;
+  PinnedBuf<unsigned int> h_cand_count;
+  Event ev_tail[3], ev_end, ev_done;
+  Event ev_reset;            /* the set's count zeroed */
+  /* seal during init */
+  DevBuf<uint4> d_seal_dig;
+  PinnedBuf<uint8_t> h_seal_dig;
+  /* POST_SEAL_DEBUG: the stream kernel timed per batch, printed at the end */
+  Event ev_seal[2];
+};
+
 struct PostInitSession {
   PostInitConfig cfg;
   std::string data_dir;
@@ -277,16 +301,13 @@ struct PostInitSession {
   uint64_t batch_seq = 0;   /* batches processed (self-check period) */
   uint32_t gap_shift = 0;
   uint64_t batch = 0;       /* labels per launch */
-  uint32_t *d_scratch = nullptr;
-  uint8_t *d_out = nullptr; /* batch output (16 B per label) */
-  uint8_t *d_all = nullptr; /* whole-range output kept on device (small) */
+  DevBuf<uint32_t> d_scratch;
+  DevBuf<uint8_t> d_all;    /* whole-range output kept on device (small) */
   bool keep_all = false;
-  PostVrfCandidate *d_cand = nullptr;
-  unsigned int *d_cand_count = nullptr;
-  uint32_t *d_xbuf = nullptr; /* 128 B per batch task (3-kernel staging) */
-  uint8_t *h_batch = nullptr; /* pinned */
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<uint32_t> d_xbuf;  /* 128 B per batch task (3-kernel staging) */
+  uint32_t cand_cap = 0;
+  OutputSet set[2];
+  Event ev0, ev1;
   double last_kernel_ms = 0; /* accumulated over the last post_init_step */
 
   /* split-kernel init path (init_step_split): 0 = monolithic ROMix on
@@ -294,26 +315,13 @@ struct PostInitSession {
    * `stream_b` (and `stream_c`); 1 = the split kernels on `stream` alone
    * (measurement).  `split_chain` holds the fill of a unit behind the fill
    * of the unit before it (two streams only, the earlier schedule, A/B).
-   * Buffer set 1 and `copy_stream` double-buffer what the host reads, so
-   * batch i is processed while batch i+1 runs. */
+   * Output set 1 and `copy_stream` double-buffer what the host reads. */
   int split_streams = 0;
   bool split_chain = false;
   uint64_t unit_cursor = 0; /* units issued so far: unit u runs on stream
                                u % split_streams, across batches and calls */
   uint64_t split_batch_no = 0; /* batches issued so far: output set = & 1 */
-  uint32_t cand_cap = 0;
-  uint8_t *d_out1 = nullptr;
-  PostVrfCandidate *d_cand1 = nullptr;
-  unsigned int *d_cand_count1 = nullptr;
-  uint8_t *h_batch1 = nullptr;                       /* pinned */
-  PostVrfCandidate *h_cand[2] = {nullptr, nullptr};  /* pinned */
-  unsigned int *h_cand_count = nullptr;              /* pinned, 2 entries */
-  hipStream_t stream_b = nullptr, stream_c = nullptr, copy_stream = nullptr;
-  hipEvent_t ev_fill[4] = {nullptr, nullptr, nullptr, nullptr}; /* chain */
-  hipEvent_t ev_tail[2][3] = {{nullptr, nullptr, nullptr},
-                              {nullptr, nullptr, nullptr}};
-  hipEvent_t ev_end[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-  hipEvent_t ev_reset[2] = {nullptr, nullptr}; /* count of set i zeroed */
+  Event ev_fill[4];            /* chain */
 
   /* seal during init (post_init_enable_seal); all unused and
    * nothing of it queued while seal_on is false */
@@ -323,55 +331,21 @@ struct PostInitSession {
   uint64_t seal_first_page = 0;
   uint64_t seal_pos = 0;     /* relative position the device carry stands at */
   uint64_t seal_launches = 0; /* carry in = launches & 1, out = the other */
-  SealCarry *d_seal_carry = nullptr;                 /* two */
-  uint4 *d_seal_dig[2] = {nullptr, nullptr};         /* per output set */
-  uint8_t *h_seal_dig[2] = {nullptr, nullptr};       /* pinned */
-  /* POST_SEAL_DEBUG: the stream kernel timed per batch, printed at the end */
-  hipEvent_t ev_seal[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  DevBuf<SealCarry> d_seal_carry; /* two */
   double seal_ms = 0, seal_ms_max = 0;
   uint64_t seal_timed = 0;
 
+  /* declared last, so destroyed first (hip_owned.h) */
+  Stream stream, stream_b, stream_c, copy_stream;
+
+  /* every stream on its own: nothing relies on one stream's end implying
+   * another's */
+  void sync_streams() {
+    for (Stream *st : {&stream, &stream_b, &stream_c, &copy_stream})
+      if (st->get()) (void)hipStreamSynchronize(st->get());
+  }
   ~PostInitSession() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (stream_b) (void)hipStreamSynchronize(stream_b);
-    if (stream_c) (void)hipStreamSynchronize(stream_c);
-    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-    for (int i = 0; i < 4; i++)
-      if (ev_fill[i]) (void)hipEventDestroy(ev_fill[i]);
-    for (int i = 0; i < 2; i++) {
-      for (int k = 0; k < 3; k++)
-        if (ev_tail[i][k]) (void)hipEventDestroy(ev_tail[i][k]);
-      if (ev_reset[i]) (void)hipEventDestroy(ev_reset[i]);
-      if (ev_end[i]) (void)hipEventDestroy(ev_end[i]);
-      if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
-      if (h_cand[i]) (void)hipHostFree(h_cand[i]);
-    }
-    if (stream_b) (void)hipStreamDestroy(stream_b);
-    if (stream_c) (void)hipStreamDestroy(stream_c);
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    if (d_out1) (void)hipFree(d_out1);
-    if (d_cand1) (void)hipFree(d_cand1);
-    if (d_cand_count1) (void)hipFree(d_cand_count1);
-    if (h_batch1) (void)hipHostFree(h_batch1);
-    if (h_cand_count) (void)hipHostFree(h_cand_count);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (d_scratch) (void)hipFree(d_scratch);
-    if (d_out) (void)hipFree(d_out);
-    if (d_all) (void)hipFree(d_all);
-    if (d_cand) (void)hipFree(d_cand);
-    if (d_cand_count) (void)hipFree(d_cand_count);
-    if (d_xbuf) (void)hipFree(d_xbuf);
-    if (h_batch) (void)hipHostFree(h_batch);
-    if (d_seal_carry) (void)hipFree(d_seal_carry);
-    for (int i = 0; i < 2; i++) {
-      if (d_seal_dig[i]) (void)hipFree(d_seal_dig[i]);
-      if (h_seal_dig[i]) (void)hipHostFree(h_seal_dig[i]);
-    }
-    for (int i = 0; i < 2; i++)
-      for (int k = 0; k < 2; k++)
-        if (ev_seal[i][k]) (void)hipEventDestroy(ev_seal[i][k]);
+    sync_streams(); /* they wait on each other's events: all, then release */
     if (seal_fd >= 0) (void)::close(seal_fd);
   }
 };
@@ -482,13 +456,14 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
   s->lanes = lanes;
   s->batch = std::min<uint64_t>(range, lanes * 4);
 
-  HIP_TRY(hipMalloc(&s->d_scratch, (size_t)lanes * per_lane));
+  HIP_TRY(s->d_scratch.alloc((size_t)lanes * per_lane));
   uint64_t keep_bytes = range * POST_LABEL_SIZE;
   s->keep_all = s->data_dir.empty() && keep_bytes <= (8ull << 30);
   if (s->keep_all) {
-    HIP_TRY(hipMalloc(&s->d_all, (size_t)keep_bytes));
+    HIP_TRY(s->d_all.alloc((size_t)keep_bytes));
   }
-  HIP_TRY(hipMalloc(&s->d_out, (size_t)s->batch * POST_LABEL_SIZE));
+  const size_t batch_bytes = (size_t)s->batch * POST_LABEL_SIZE;
+  HIP_TRY(s->set[0].d_out.alloc(batch_bytes));
   /* The tail appends one candidate per workgroup per launch, whatever the
    * threshold.  The split path launches one tail per unit; units are whole
    * workgroups but for the last of a batch, so a batch appends at most
@@ -496,13 +471,13 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
    * given lags the host's by the batches in flight. */
   s->cand_cap =
       (uint32_t)std::max<uint64_t>(CAND_CAP, s->batch / 64 + 16);
-  HIP_TRY(hipMalloc(&s->d_cand, sizeof(PostVrfCandidate) * s->cand_cap));
+  const size_t cand_bytes = sizeof(PostVrfCandidate) * s->cand_cap;
+  HIP_TRY(s->set[0].d_cand.alloc(cand_bytes));
   /* at least one unit per stream of the split path: lanes tasks */
-  HIP_TRY(hipMalloc(&s->d_xbuf,
-                    (size_t)std::max<uint64_t>(s->batch, lanes) * 128));
-  HIP_TRY(hipMalloc(&s->d_cand_count, sizeof(unsigned int)));
-  HIP_TRY(hipHostMalloc(&s->h_batch, (size_t)s->batch * POST_LABEL_SIZE));
-  HIP_TRY(hipStreamCreate(&s->stream));
+  HIP_TRY(s->d_xbuf.alloc((size_t)std::max<uint64_t>(s->batch, lanes) * 128));
+  HIP_TRY(s->set[0].d_cand_count.alloc(sizeof(unsigned int)));
+  HIP_TRY(s->set[0].h_batch.alloc(batch_bytes));
+  HIP_TRY(s->stream.create());
 
   /* POST_ROMIX_MIX: unset or free3 = phase-mixed wherever the lean gap-1
    * kernel applies, three free-running streams over thirds of the slots
@@ -527,32 +502,26 @@ int post_init_new(const PostInitConfig *cfg, PostInitSession **out) {
         s->split_streams == 2 && mx && std::strcmp(mx, "chain") == 0;
   }
   if (s->split_streams) {
-    if (!s->keep_all)
-      HIP_TRY(hipMalloc(&s->d_out1, (size_t)s->batch * POST_LABEL_SIZE));
-    HIP_TRY(hipMalloc(&s->d_cand1, sizeof(PostVrfCandidate) * s->cand_cap));
-    HIP_TRY(hipMalloc(&s->d_cand_count1, sizeof(unsigned int)));
-    HIP_TRY(hipHostMalloc(&s->h_batch1, (size_t)s->batch * POST_LABEL_SIZE));
-    HIP_TRY(hipHostMalloc(&s->h_cand_count, 2 * sizeof(unsigned int)));
-    for (int i = 0; i < 2; i++) {
-      HIP_TRY(hipHostMalloc(&s->h_cand[i],
-                            sizeof(PostVrfCandidate) * s->cand_cap));
-      HIP_TRY(hipEventCreate(&s->ev_end[i]));
-      HIP_TRY(hipEventCreateWithFlags(&s->ev_done[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&s->ev_reset[i],
-                                      hipEventDisableTiming));
+    if (!s->keep_all) HIP_TRY(s->set[1].d_out.alloc(batch_bytes));
+    HIP_TRY(s->set[1].d_cand.alloc(cand_bytes));
+    HIP_TRY(s->set[1].d_cand_count.alloc(sizeof(unsigned int)));
+    HIP_TRY(s->set[1].h_batch.alloc(batch_bytes));
+    for (OutputSet &o : s->set) {
+      HIP_TRY(o.h_cand_count.alloc(sizeof(unsigned int)));
+      HIP_TRY(o.h_cand.alloc(cand_bytes));
+      HIP_TRY(o.ev_end.create());
+      HIP_TRY(o.ev_done.create(hipEventDisableTiming));
+      HIP_TRY(o.ev_reset.create(hipEventDisableTiming));
       for (int k = 0; k < s->split_streams; k++)
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_tail[i][k],
-                                        hipEventDisableTiming));
+        HIP_TRY(o.ev_tail[k].create(hipEventDisableTiming));
     }
     if (s->split_chain)
-      for (int i = 0; i < 4; i++)
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_fill[i],
-                                        hipEventDisableTiming));
+      for (Event &e : s->ev_fill) HIP_TRY(e.create(hipEventDisableTiming));
     /* with the copy stream at most four streams: the hardware queues a
      * process gets by default */
-    if (s->split_streams >= 2) HIP_TRY(hipStreamCreate(&s->stream_b));
-    if (s->split_streams >= 3) HIP_TRY(hipStreamCreate(&s->stream_c));
-    HIP_TRY(hipStreamCreate(&s->copy_stream));
+    if (s->split_streams >= 2) HIP_TRY(s->stream_b.create());
+    if (s->split_streams >= 3) HIP_TRY(s->stream_c.create());
+    HIP_TRY(s->copy_stream.create());
   }
 
   if (!s->data_dir.empty()) {
@@ -806,32 +775,32 @@ static uint64_t seal_range_pages(const PostInitSession *s) {
 }
 
 /* Queue the stream kernel over the batch at relative position pos that lies
- * at d_labels, and the copy of its digests to the pinned buffer of `set`. */
-static int seal_launch(PostInitSession *s, hipStream_t stream, int set,
+ * at d_labels, and the copy of its digests to the pinned buffer of `o`. */
+static int seal_launch(PostInitSession *s, hipStream_t stream, OutputSet &o,
                        uint64_t pos, uint64_t count, const uint8_t *d_labels) {
   SealStreamArgs a;
   a.labels = (const uint4 *)d_labels;
   a.g0 = s->range_start + pos;
   a.count = count;
   a.stream_end = (uint64_t)s->cfg.num_units * s->cfg.labels_per_unit;
-  a.carry_in = s->d_seal_carry + (s->seal_launches & 1);
-  a.carry_out = s->d_seal_carry + ((s->seal_launches + 1) & 1);
-  a.digests = s->d_seal_dig[set];
-  if (s->ev_seal[set][0]) HIP_TRY(hipEventRecord(s->ev_seal[set][0], stream));
+  a.carry_in = s->d_seal_carry.get() + (s->seal_launches & 1);
+  a.carry_out = s->d_seal_carry.get() + ((s->seal_launches + 1) & 1);
+  a.digests = o.d_seal_dig.get();
+  if (o.ev_seal[0].get()) HIP_TRY(hipEventRecord(o.ev_seal[0].get(), stream));
   HIP_TRY(poste_launch_seal_stream_kernel(&a, stream));
-  if (s->ev_seal[set][1]) HIP_TRY(hipEventRecord(s->ev_seal[set][1], stream));
+  if (o.ev_seal[1].get()) HIP_TRY(hipEventRecord(o.ev_seal[1].get(), stream));
   s->seal_launches++;
   s->seal_pos = pos + count;
   const uint64_t lanes =
       (a.g0 + count - 1) / SEALP_PAGE - a.g0 / SEALP_PAGE + 1;
-  HIP_TRY(hipMemcpyAsync(s->h_seal_dig[set], s->d_seal_dig[set],
+  HIP_TRY(hipMemcpyAsync(o.h_seal_dig.get(), o.d_seal_dig.get(),
                          lanes * SEALP_DIGEST, hipMemcpyDeviceToHost, stream));
   return POST_OK;
 }
 
 /* The batch's labels are in the files: append the digests of the pages that
  * closed in it.  The caller advances `written` only after this. */
-static int seal_commit(PostInitSession *s, int set, uint64_t pos,
+static int seal_commit(PostInitSession *s, OutputSet &o, uint64_t pos,
                        uint64_t count) {
   const uint64_t g0 = s->range_start + pos, end = g0 + count;
   const uint64_t total = (uint64_t)s->cfg.num_units * s->cfg.labels_per_unit;
@@ -841,8 +810,8 @@ static int seal_commit(PostInitSession *s, int set, uint64_t pos,
       (end % SEALP_PAGE == 0 || end == total) ? lanes : lanes - 1;
   const size_t want = (size_t)(closed * SEALP_DIGEST);
   float ms = 0;
-  if (s->ev_seal[set][0] &&
-      hipEventElapsedTime(&ms, s->ev_seal[set][0], s->ev_seal[set][1]) ==
+  if (o.ev_seal[0].get() &&
+      hipEventElapsedTime(&ms, o.ev_seal[0].get(), o.ev_seal[1].get()) ==
           hipSuccess) {
     s->seal_ms += ms;
     s->seal_ms_max = std::max<double>(s->seal_ms_max, ms);
@@ -853,7 +822,7 @@ static int seal_commit(PostInitSession *s, int set, uint64_t pos,
   size_t put = 0;
   while (put < want) {
     const ssize_t w =
-        ::pwrite(s->seal_fd, s->h_seal_dig[set] + put, want - put, at + put);
+        ::pwrite(s->seal_fd, o.h_seal_dig.get() + put, want - put, at + put);
     if (w <= 0) {
       if (w < 0 && errno == EINTR) continue;
       set_error("short write to " +
@@ -993,15 +962,142 @@ int post_init_enable_seal(PostInitSession *s) {
   if (rc != POST_OK) return rc;
   /* a batch touches at most batch / 1024 + 2 pages */
   const size_t dig_bytes = (size_t)((s->batch / SEALP_PAGE + 2) * SEALP_DIGEST);
-  HIP_TRY(hipMalloc(&s->d_seal_carry, 2 * sizeof(SealCarry)));
-  HIP_TRY(hipMemset(s->d_seal_carry, 0, 2 * sizeof(SealCarry)));
+  HIP_TRY(s->d_seal_carry.alloc(2 * sizeof(SealCarry)));
+  HIP_TRY(hipMemset(s->d_seal_carry.get(), 0, 2 * sizeof(SealCarry)));
   for (int i = 0; i < (s->split_streams ? 2 : 1); i++) {
-    HIP_TRY(hipMalloc(&s->d_seal_dig[i], dig_bytes));
-    HIP_TRY(hipHostMalloc(&s->h_seal_dig[i], dig_bytes));
+    OutputSet &o = s->set[i];
+    HIP_TRY(o.d_seal_dig.alloc(dig_bytes));
+    HIP_TRY(o.h_seal_dig.alloc(dig_bytes));
     if (getenv("POST_SEAL_DEBUG"))
-      for (int k = 0; k < 2; k++) HIP_TRY(hipEventCreate(&s->ev_seal[i][k]));
+      for (Event &e : o.ev_seal) HIP_TRY(e.create());
   }
   s->seal_on = true;
+  return POST_OK;
+}
+
+/* ------------------- host half of an init batch -------------------
+ *
+ * Shared by the monolithic step, the split step and the nonce search past
+ * the end (nonce_only_batch), so the three cannot drift apart. */
+
+/* the LabelKernelArgs fields common to every launch of a session */
+static LabelKernelArgs init_label_args(const PostInitSession *s) {
+  LabelKernelArgs args;
+  std::memset(&args, 0, sizeof(args));
+  load_commitment_words(s->commitment, args.commitment_le);
+  args.scrypt_n = s->cfg.scrypt_n;
+  args.gap_shift = s->gap_shift;
+  args.scratch = s->d_scratch.get();
+  args.scratch_lanes = s->lanes;
+  args.has_difficulty = 1;
+  args.cand_cap = s->cand_cap;
+  return args;
+}
+
+/* the threshold a call starts from: the session's minimum, or all ones */
+static void load_running_minimum(PostInitSession *s, uint8_t cur[32]) {
+  std::memset(cur, 0xff, 32); /* track the global minimum */
+  std::lock_guard<std::mutex> lk(s->nonce_mu);
+  if (s->nonce_found) std::memcpy(cur, s->nonce_label, 32);
+}
+
+/* Merge n device candidates into the session's running minimum, of which
+ * cur_difficulty is the caller's copy: lower label wins, a tie goes to the
+ * lower index.  Returns whether the minimum improved. */
+static bool merge_candidates(PostInitSession *s, const PostVrfCandidate *cands,
+                             unsigned int n, uint8_t cur_difficulty[32]) {
+  bool improved = false;
+  std::lock_guard<std::mutex> lk(s->nonce_mu);
+  for (unsigned int i = 0; i < n; i++) {
+    uint8_t lab[32];
+    for (int k = 0; k < 8; k++) {
+      uint32_t w = cands[i].label_be[k];
+      lab[4 * k] = (uint8_t)(w >> 24);
+      lab[4 * k + 1] = (uint8_t)(w >> 16);
+      lab[4 * k + 2] = (uint8_t)(w >> 8);
+      lab[4 * k + 3] = (uint8_t)w;
+    }
+    int c = std::memcmp(lab, cur_difficulty, 32);
+    if (!s->nonce_found || c < 0 ||
+        (c == 0 && cands[i].index < s->nonce_idx)) {
+      s->nonce_found = true;
+      s->nonce_idx = cands[i].index;
+      std::memcpy(s->nonce_label, lab, 32);
+      std::memcpy(cur_difficulty, lab, 32);
+      improved = true;
+    }
+  }
+  return improved;
+}
+
+/* Reference-label self-check (ErrReferenceLabelMismatch semantics,
+ * activation/post.go:299-312), one object per post_init_step call.  begin()
+ * is called once a batch is queued and before the host waits for it: the
+ * reference label computes on the host WHILE the kernel runs (a ~5 ms scrypt
+ * that would otherwise sit on the critical path between launches).
+ * POST_SELFCHECK_PERIOD=k checks every k-th batch instead — with 8 ranks per
+ * node the per-rank host scrypt otherwise contends for the same host cores
+ * (SCALE readiness); detection latency rises k batches,
+ * coverage semantics are unchanged.  finish_batch compares. */
+struct SelfCheck {
+  uint64_t period = 1;
+  bool on = false;    /* this batch is checked */
+  uint64_t probe = 0; /* label of the batch that is compared */
+  int ref_rc = 0;
+  uint8_t ref[32];
+
+  SelfCheck() {
+    const char *env = getenv("POST_SELFCHECK_PERIOD");
+    const long v = env ? strtol(env, nullptr, 10) : 1;
+    if (v > 1) period = (uint64_t)v;
+  }
+  void begin(PostInitSession *s, uint64_t pos, uint64_t count) {
+    on = (s->batch_seq++ % period) == 0;
+    probe = count / 2;
+    ref_rc = on ? poste::host_label(s->commitment,
+                                    s->range_start + pos + probe,
+                                    s->cfg.scrypt_n, ref)
+                : 0;
+  }
+};
+
+/* The batch at relative position pos has arrived in `o` and its candidates
+ * are merged: check it, persist it, count it. */
+static int finish_batch(PostInitSession *s, OutputSet &o, const SelfCheck &sc,
+                        uint64_t pos, uint64_t count, bool nonce_improved,
+                        uint64_t *done) {
+  int rc;
+  /* persist an improved running minimum immediately: metadata is the
+   * only carrier of the shard-local minimum across kill+resume (the
+   * creation-time write has no nonce yet, and a completed-at-exit-only
+   * write loses it on any interrupt — the cfg4 soak caught exactly
+   * that).  Improvements are rare (~log of batches), so this is a few
+   * small rewrites per session. */
+  if (nonce_improved && !s->data_dir.empty()) {
+    rc = write_metadata(s);
+    if (rc != POST_OK) return rc;
+  }
+  if (sc.ref_rc != 0) {
+    set_error("host reference label failed");
+    return POST_ERR;
+  }
+  if (sc.on && std::memcmp(sc.ref, o.h_batch.get() + sc.probe * POST_LABEL_SIZE,
+                           POST_LABEL_SIZE) != 0) {
+    set_error("reference label mismatch: device labels diverge from the "
+              "host reference (ErrReferenceLabelMismatch)");
+    return POST_ERR;
+  }
+  if (!s->data_dir.empty()) {
+    rc = write_batch_files(s, s->range_start + pos, count, o.h_batch.get());
+    if (rc != POST_OK) return rc;
+  }
+  /* digests only behind their labels (a seal needs a data dir) */
+  if (s->seal_on) {
+    rc = seal_commit(s, o, pos, count);
+    if (rc != POST_OK) return rc;
+  }
+  s->written.store(pos + count);
+  *done += count;
   return POST_OK;
 }
 
@@ -1031,62 +1127,27 @@ int post_init_enable_seal(PostInitSession *s) {
  * a drain.  The pipeline drains at the end of the call, on cancel and on
  * error.  The threshold a tail is given lags the host's by the batch in
  * flight; the host merge compares exactly, so the nonce is the same. */
-static int init_step_split(PostInitSession *s, uint64_t max_labels,
-                           uint64_t *done) {
+static int init_step_split(PostInitSession *s, SelfCheck &sc,
+                           uint64_t max_labels, uint64_t *done) {
   const int ns = s->split_streams;
   /* slots per unit: one stream's share, whole 64-quad workgroups */
   const uint64_t unit = s->lanes / (uint64_t)ns / 64 * 64;
-  hipStream_t st[3] = {s->stream, s->stream_b, s->stream_c};
-  uint8_t *const d_outs[2] = {s->d_out, s->d_out1};
-  uint8_t *const h_batches[2] = {s->h_batch, s->h_batch1};
-  PostVrfCandidate *const d_cands[2] = {s->d_cand, s->d_cand1};
-  unsigned int *const d_counts[2] = {s->d_cand_count, s->d_cand_count1};
+  hipStream_t st[3] = {s->stream.get(), s->stream_b.get(), s->stream_c.get()};
+  const hipStream_t copy_stream = s->copy_stream.get();
 
-  /* End of call, cancel and error all leave through here: every stream is
-   * synchronised on its own, so nothing relies on one stream's end
-   * implying another's.  Every event a stream waits for is recorded before
-   * the wait is queued, so a call that fails half-way through issue()
-   * leaves no stream waiting for a record that never comes. */
-  auto drain = [&] {
-    for (int k = 0; k < ns; k++) (void)hipStreamSynchronize(st[k]);
-    (void)hipStreamSynchronize(s->copy_stream);
-  };
-#define SPLIT_TRY(expr)                                                        \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      drain();                                                                 \
-      return hip_fail(#expr, _e);                                              \
-    }                                                                          \
-  } while (0)
-
-  LabelKernelArgs args;
-  std::memset(&args, 0, sizeof(args));
-  load_commitment_words(s->commitment, args.commitment_le);
-  args.scrypt_n = s->cfg.scrypt_n;
-  args.gap_shift = s->gap_shift;
-  args.scratch = s->d_scratch;
-  args.scratch_lanes = s->lanes;
-  args.has_difficulty = 1;
-  args.cand_cap = s->cand_cap;
+  LabelKernelArgs args = init_label_args(s);
   RomixPhaseArgs ph;
   std::memset(&ph, 0, sizeof(ph));
-  ph.scratch = s->d_scratch;
+  ph.scratch = s->d_scratch.get();
   ph.scratch_lanes = s->lanes;
   ph.slot_count = unit;
   ph.scrypt_n = s->cfg.scrypt_n;
 
   uint8_t cur_difficulty[32];
-  std::memset(cur_difficulty, 0xff, 32); /* track the global minimum */
-  {
-    std::lock_guard<std::mutex> lk(s->nonce_mu);
-    if (s->nonce_found) std::memcpy(cur_difficulty, s->nonce_label, 32);
-  }
-  const char *sp_env = getenv("POST_SELFCHECK_PERIOD");
-  long selfcheck_period = sp_env ? strtol(sp_env, nullptr, 10) : 1;
-  if (selfcheck_period < 1) selfcheck_period = 1;
+  load_running_minimum(s, cur_difficulty);
 
-  if (!s->ev0) SPLIT_TRY(hipEventCreate(&s->ev0));
+  if (!s->ev0.get()) HIP_TRY(s->ev0.create());
+  const hipEvent_t ev0 = s->ev0.get();
   s->last_kernel_ms = 0;
 
   struct Batch {
@@ -1110,10 +1171,11 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
      * ends drained, so the first batch of a call may start on any stream. */
     b.set = (int)(s->split_batch_no++ & 1);
     b.max_cand = 0;
-    uint8_t *out =
-        s->keep_all ? s->d_all + b.pos * POST_LABEL_SIZE : d_outs[b.set];
-    args.cand = d_cands[b.set];
-    args.cand_count = d_counts[b.set];
+    OutputSet &o = s->set[b.set];
+    uint8_t *out = s->keep_all ? s->d_all.get() + b.pos * POST_LABEL_SIZE
+                               : o.d_out.get();
+    args.cand = o.d_cand.get();
+    args.cand_count = o.d_cand_count.get();
     difficulty_to_be_words(cur_difficulty, args.difficulty_be);
     /* The batch's candidate count is zeroed on the stream of its first
      * unit, whose tails follow in stream order.  Every other stream's
@@ -1121,9 +1183,9 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
      * the reset (this stream may still be busy with the batch before), so
      * each of them waits for ev_reset before its first tail of the batch. */
     const int k0 = (int)(s->unit_cursor % (uint64_t)ns);
-    SPLIT_TRY(hipMemsetAsync(d_counts[b.set], 0, sizeof(unsigned int),
-                             st[k0]));
-    if (ns > 1) SPLIT_TRY(hipEventRecord(s->ev_reset[b.set], st[k0]));
+    HIP_TRY(hipMemsetAsync(o.d_cand_count.get(), 0, sizeof(unsigned int),
+                           st[k0]));
+    if (ns > 1) HIP_TRY(hipEventRecord(o.ev_reset.get(), st[k0]));
     /* units of equal size, whole workgroups: a ragged batch costs every
      * unit a few labels, not one more round for a handful of them */
     const uint64_t nunits = (b.count + unit - 1) / unit;
@@ -1136,25 +1198,25 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
       args.start = s->range_start + b.pos + off;
       args.count = c;
       /* stream k owns slots and xbuf tasks [k * unit, (k + 1) * unit) */
-      args.xbuf = s->d_xbuf + (uint64_t)k * unit * 32; /* 128 B per task */
+      args.xbuf = s->d_xbuf.get() + (uint64_t)k * unit * 32; /* 128 B a task */
       args.out = out + off * POST_LABEL_SIZE;
       ph.xbuf = args.xbuf;
       ph.slot_base = (uint64_t)k * unit;
       ph.count = c;
       /* the streams are idle when a call begins and this unit is queued
        * first, so ev0 marks the start of the call's first kernel */
-      if (issued == 0) SPLIT_TRY(hipEventRecord(s->ev0, st[k]));
-      SPLIT_TRY(poste_launch_label_prologue(&args, blocks, st[k]));
+      if (issued == 0) HIP_TRY(hipEventRecord(ev0, st[k]));
+      HIP_TRY(poste_launch_label_prologue(&args, blocks, st[k]));
       if (s->split_chain && issued > 0)
-        SPLIT_TRY(hipStreamWaitEvent(
-            st[k], s->ev_fill[(s->unit_cursor - 1) & 3], 0));
-      SPLIT_TRY(poste_launch_romix_fill(&ph, st[k]));
+        HIP_TRY(hipStreamWaitEvent(
+            st[k], s->ev_fill[(s->unit_cursor - 1) & 3].get(), 0));
+      HIP_TRY(poste_launch_romix_fill(&ph, st[k]));
       if (s->split_chain)
-        SPLIT_TRY(hipEventRecord(s->ev_fill[s->unit_cursor & 3], st[k]));
-      SPLIT_TRY(poste_launch_romix_mix(&ph, st[k]));
+        HIP_TRY(hipEventRecord(s->ev_fill[s->unit_cursor & 3].get(), st[k]));
+      HIP_TRY(poste_launch_romix_mix(&ph, st[k]));
       if (k != k0 && !used[k])
-        SPLIT_TRY(hipStreamWaitEvent(st[k], s->ev_reset[b.set], 0));
-      SPLIT_TRY(poste_launch_label_tail(&args, blocks, st[k]));
+        HIP_TRY(hipStreamWaitEvent(st[k], o.ev_reset.get(), 0));
+      HIP_TRY(poste_launch_label_tail(&args, blocks, st[k]));
       b.max_cand += blocks;
       used[k] = true;
       s->unit_cursor++;
@@ -1167,33 +1229,28 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
      * and the last unit. */
     for (int k = 0; k < ns; k++) {
       if (!used[k]) continue;
-      SPLIT_TRY(hipEventRecord(s->ev_tail[b.set][k], st[k]));
-      SPLIT_TRY(hipStreamWaitEvent(s->copy_stream, s->ev_tail[b.set][k], 0));
+      HIP_TRY(hipEventRecord(o.ev_tail[k].get(), st[k]));
+      HIP_TRY(hipStreamWaitEvent(copy_stream, o.ev_tail[k].get(), 0));
     }
-    SPLIT_TRY(hipEventRecord(s->ev_end[b.set], s->copy_stream));
+    HIP_TRY(hipEventRecord(o.ev_end.get(), copy_stream));
     /* the seal of the batch: behind every tail of it like the copies, and
      * behind the seal of the batch before, which left the carry */
     if (s->seal_on) {
-      const int rc =
-          seal_launch(s, s->copy_stream, b.set, b.pos, b.count, out);
-      if (rc != POST_OK) {
-        drain();
-        return rc;
-      }
+      const int rc = seal_launch(s, copy_stream, o, b.pos, b.count, out);
+      if (rc != POST_OK) return rc;
     }
-    SPLIT_TRY(hipMemcpyAsync(h_batches[b.set], out,
-                             b.count * POST_LABEL_SIZE, hipMemcpyDeviceToHost,
-                             s->copy_stream));
-    SPLIT_TRY(hipMemcpyAsync(s->h_cand_count + b.set, d_counts[b.set],
-                             sizeof(unsigned int), hipMemcpyDeviceToHost,
-                             s->copy_stream));
+    HIP_TRY(hipMemcpyAsync(o.h_batch.get(), out, b.count * POST_LABEL_SIZE,
+                           hipMemcpyDeviceToHost, copy_stream));
+    HIP_TRY(hipMemcpyAsync(o.h_cand_count.get(), o.d_cand_count.get(),
+                           sizeof(unsigned int), hipMemcpyDeviceToHost,
+                           copy_stream));
     /* every candidate the batch can have appended, so nothing is fetched
      * later behind the next batch's copies */
     b.max_cand = std::min(b.max_cand, s->cand_cap);
-    SPLIT_TRY(hipMemcpyAsync(s->h_cand[b.set], d_cands[b.set],
-                             sizeof(PostVrfCandidate) * b.max_cand,
-                             hipMemcpyDeviceToHost, s->copy_stream));
-    SPLIT_TRY(hipEventRecord(s->ev_done[b.set], s->copy_stream));
+    HIP_TRY(hipMemcpyAsync(o.h_cand.get(), o.d_cand.get(),
+                           sizeof(PostVrfCandidate) * b.max_cand,
+                           hipMemcpyDeviceToHost, copy_stream));
+    HIP_TRY(hipEventRecord(o.ev_done.get(), copy_stream));
     last_set = b.set;
     b.live = true;
     return POST_OK;
@@ -1202,110 +1259,63 @@ static int init_step_split(PostInitSession *s, uint64_t max_labels,
   /* host side of one batch, as on the monolithic path */
   auto process = [&](Batch &b) -> int {
     b.live = false;
-    const bool do_selfcheck =
-        (s->batch_seq++ % (uint64_t)selfcheck_period) == 0;
-    const uint64_t probe = b.count / 2;
-    uint8_t ref[32];
-    /* the host reference label computes while the device runs */
-    const int ref_rc =
-        do_selfcheck
-            ? poste::host_label(s->commitment, s->range_start + b.pos + probe,
-                                s->cfg.scrypt_n, ref)
-            : 0;
-    SPLIT_TRY(hipEventSynchronize(s->ev_done[b.set]));
-    const unsigned int take = std::min(s->h_cand_count[b.set], b.max_cand);
-    const PostVrfCandidate *cands = s->h_cand[b.set];
-    bool nonce_improved = false;
-    if (take > 0) {
-      std::lock_guard<std::mutex> lk(s->nonce_mu);
-      for (unsigned int i = 0; i < take; i++) {
-        uint8_t lab[32];
-        for (int k = 0; k < 8; k++) {
-          uint32_t w = cands[i].label_be[k];
-          lab[4 * k] = (uint8_t)(w >> 24);
-          lab[4 * k + 1] = (uint8_t)(w >> 16);
-          lab[4 * k + 2] = (uint8_t)(w >> 8);
-          lab[4 * k + 3] = (uint8_t)w;
-        }
-        int c = std::memcmp(lab, cur_difficulty, 32);
-        if (!s->nonce_found || c < 0 ||
-            (c == 0 && cands[i].index < s->nonce_idx)) {
-          s->nonce_found = true;
-          s->nonce_idx = cands[i].index;
-          std::memcpy(s->nonce_label, lab, 32);
-          std::memcpy(cur_difficulty, lab, 32);
-          nonce_improved = true;
-        }
-      }
-    }
-    int rc = POST_OK;
-    /* an improved minimum is persisted at once (see post_init_step) */
-    if (nonce_improved && !s->data_dir.empty()) rc = write_metadata(s);
-    if (rc == POST_OK && ref_rc != 0) {
-      set_error("host reference label failed");
-      rc = POST_ERR;
-    }
-    if (rc == POST_OK && do_selfcheck &&
-        std::memcmp(ref, h_batches[b.set] + probe * POST_LABEL_SIZE,
-                    POST_LABEL_SIZE) != 0) {
-      set_error("reference label mismatch: device labels diverge from the "
-                "host reference (ErrReferenceLabelMismatch)");
-      rc = POST_ERR;
-    }
-    if (rc == POST_OK && !s->data_dir.empty())
-      rc = write_batch_files(s, s->range_start + b.pos, b.count,
-                             h_batches[b.set]);
-    /* digests only behind their labels */
-    if (rc == POST_OK && s->seal_on)
-      rc = seal_commit(s, b.set, b.pos, b.count);
-    if (rc != POST_OK) {
-      drain();
-      return rc;
-    }
-    s->written.store(b.pos + b.count);
-    *done += b.count;
-    return POST_OK;
+    OutputSet &o = s->set[b.set];
+    sc.begin(s, b.pos, b.count);
+    HIP_TRY(hipEventSynchronize(o.ev_done.get()));
+    const unsigned int take = std::min(*o.h_cand_count.get(), b.max_cand);
+    const bool improved =
+        merge_candidates(s, o.h_cand.get(), take, cur_difficulty);
+    return finish_batch(s, o, sc, b.pos, b.count, improved, done);
   };
 
-  const uint64_t range = s->range_end - s->range_start;
-  uint64_t pos = s->written.load(); /* relative position (resume) */
-  const uint64_t target = std::min(range, pos + max_labels);
-  Batch inflight[2];
-  int cur = 0;
-  bool cancelled = false;
-  while (pos < target) {
-    /* cancel is seen between batches only: a batch is either issued whole,
-     * with all its events, or not at all */
-    if (s->cancel.load()) {
-      cancelled = true;
-      break;
+  auto run = [&]() -> int {
+    const uint64_t range = s->range_end - s->range_start;
+    uint64_t pos = s->written.load(); /* relative position (resume) */
+    const uint64_t target = std::min(range, pos + max_labels);
+    Batch inflight[2];
+    int cur = 0;
+    bool cancelled = false;
+    while (pos < target) {
+      /* cancel is seen between batches only: a batch is either issued
+       * whole, with all its events, or not at all */
+      if (s->cancel.load()) {
+        cancelled = true;
+        break;
+      }
+      Batch &b = inflight[cur];
+      b.pos = pos;
+      b.count = std::min(s->batch, target - pos);
+      int rc = issue(b);
+      if (rc != POST_OK) return rc;
+      pos += b.count;
+      if (inflight[cur ^ 1].live) {
+        rc = process(inflight[cur ^ 1]);
+        if (rc != POST_OK) return rc;
+      }
+      cur ^= 1;
     }
-    Batch &b = inflight[cur];
-    b.pos = pos;
-    b.count = std::min(s->batch, target - pos);
-    int rc = issue(b);
-    if (rc != POST_OK) return rc;
-    pos += b.count;
+    /* the batch still in flight is complete work: hand it over, cancelled
+     * or not, so `written` covers exactly what reached the sink or the
+     * files */
     if (inflight[cur ^ 1].live) {
-      rc = process(inflight[cur ^ 1]);
+      int rc = process(inflight[cur ^ 1]);
       if (rc != POST_OK) return rc;
     }
-    cur ^= 1;
-  }
-  /* the batch still in flight is complete work: hand it over, cancelled or
-   * not, so `written` covers exactly what reached the sink or the files */
-  if (inflight[cur ^ 1].live) {
-    int rc = process(inflight[cur ^ 1]);
-    if (rc != POST_OK) return rc;
-  }
-  drain();
-  if (last_set >= 0) {
+    return cancelled ? POST_ERR_CANCELLED : POST_OK;
+  };
+
+  /* End of call, cancel and error all drain here.  Every event a stream
+   * waits for is recorded before the wait is queued, so a call that fails
+   * half-way through issue() leaves no stream waiting for a record that
+   * never comes. */
+  const int rc = run();
+  s->sync_streams();
+  if ((rc == POST_OK || rc == POST_ERR_CANCELLED) && last_set >= 0) {
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, s->ev0, s->ev_end[last_set]);
+    (void)hipEventElapsedTime(&ms, ev0, s->set[last_set].ev_end.get());
     s->last_kernel_ms = ms;
   }
-#undef SPLIT_TRY
-  return cancelled ? POST_ERR_CANCELLED : POST_OK;
+  return rc;
 }
 
 int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
@@ -1318,39 +1328,24 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
     rc = seal_resync(s);
     if (rc != POST_OK) return rc;
   }
-  if (s->split_streams) return init_step_split(s, max_labels, done);
+  SelfCheck sc;
+  if (s->split_streams) return init_step_split(s, sc, max_labels, done);
 
-  LabelKernelArgs args;
-  std::memset(&args, 0, sizeof(args));
-  load_commitment_words(s->commitment, args.commitment_le);
-  args.scrypt_n = s->cfg.scrypt_n;
-  args.gap_shift = s->gap_shift;
-  args.xbuf = s->d_xbuf;
-  args.out_full = 0;
-  args.scratch = s->d_scratch;
-  args.scratch_lanes = s->lanes;
-  args.indices = nullptr;
-  args.commit_ids = nullptr;
-  args.commitments = nullptr;
-  args.has_difficulty = 1;
-  args.cand = s->d_cand;
-  args.cand_count = s->d_cand_count;
-  args.cand_cap = s->cand_cap;
+  OutputSet &o = s->set[0];
+  const hipStream_t stream = s->stream.get();
+  LabelKernelArgs args = init_label_args(s);
+  args.xbuf = s->d_xbuf.get();
+  args.cand = o.d_cand.get();
+  args.cand_count = o.d_cand_count.get();
 
   uint8_t cur_difficulty[32];
-  std::memset(cur_difficulty, 0xff, 32); /* track the global minimum */
-  {
-    std::lock_guard<std::mutex> lk(s->nonce_mu);
-    if (s->nonce_found) std::memcpy(cur_difficulty, s->nonce_label, 32);
-  }
+  load_running_minimum(s, cur_difficulty);
 
   const uint32_t blocks = (uint32_t)(s->lanes / 64); /* 64 quads/block */
   std::vector<PostVrfCandidate> cands(s->cand_cap);
 
-  if (!s->ev0) {
-    HIP_TRY(hipEventCreate(&s->ev0));
-    HIP_TRY(hipEventCreate(&s->ev1));
-  }
+  if (!s->ev0.get()) HIP_TRY(s->ev0.create());
+  if (!s->ev1.get()) HIP_TRY(s->ev1.create());
   s->last_kernel_ms = 0;
 
   uint64_t range = s->range_end - s->range_start;
@@ -1361,108 +1356,40 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
     uint64_t count = std::min(s->batch, target - pos);
     args.start = s->range_start + pos;
     args.count = count;
-    args.out = s->keep_all ? s->d_all + pos * POST_LABEL_SIZE : s->d_out;
+    args.out = s->keep_all ? s->d_all.get() + pos * POST_LABEL_SIZE
+                           : o.d_out.get();
     difficulty_to_be_words(cur_difficulty, args.difficulty_be);
     unsigned int zero = 0;
-    HIP_TRY(hipMemcpyAsync(s->d_cand_count, &zero, sizeof(zero),
-                           hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipEventRecord(s->ev0, s->stream));
-    HIP_TRY(poste_launch_label_kernel(&args, blocks, s->stream));
-    HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(hipMemcpyAsync(o.d_cand_count.get(), &zero, sizeof(zero),
+                           hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev0.get(), stream));
+    HIP_TRY(poste_launch_label_kernel(&args, blocks, stream));
+    HIP_TRY(hipEventRecord(s->ev1.get(), stream));
     if (s->seal_on) {
-      rc = seal_launch(s, s->stream, 0, pos, count, args.out);
+      rc = seal_launch(s, stream, o, pos, count, args.out);
       if (rc != POST_OK) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(s->h_batch, args.out, count * POST_LABEL_SIZE,
-                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(o.h_batch.get(), args.out, count * POST_LABEL_SIZE,
+                           hipMemcpyDeviceToHost, stream));
     unsigned int n_cand = 0;
-    HIP_TRY(hipMemcpyAsync(&n_cand, s->d_cand_count, sizeof(n_cand),
-                           hipMemcpyDeviceToHost, s->stream));
-    /* the reference label for this batch's self-check computes on the host
-     * WHILE the kernel runs (a ~5 ms scrypt that would otherwise sit on
-     * the critical path between launches).  POST_SELFCHECK_PERIOD=k checks
-     * every k-th batch instead — with 8 ranks per node the per-rank host
-     * scrypt otherwise contends for the same host cores (SCALE readiness,
-     * VERDICT r01 §next-3); detection latency rises k batches, coverage
-     * semantics (ErrReferenceLabelMismatch) are unchanged. */
-    const char *sp_env = getenv("POST_SELFCHECK_PERIOD");
-    long selfcheck_period = sp_env ? strtol(sp_env, nullptr, 10) : 1;
-    if (selfcheck_period < 1) selfcheck_period = 1;
-    const bool do_selfcheck = (s->batch_seq++ % (uint64_t)selfcheck_period)
-                              == 0;
-    const uint64_t probe = count / 2;
-    uint8_t ref[32];
-    const int ref_rc =
-        do_selfcheck ? poste::host_label(s->commitment, args.start + probe,
-                                         s->cfg.scrypt_n, ref)
-                     : 0;
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpyAsync(&n_cand, o.d_cand_count.get(), sizeof(n_cand),
+                           hipMemcpyDeviceToHost, stream));
+    sc.begin(s, pos, count);
+    HIP_TRY(hipStreamSynchronize(stream));
     bool nonce_improved = false;
     if (n_cand > 0) {
       unsigned int take = std::min(n_cand, s->cand_cap);
-      HIP_TRY(hipMemcpy(cands.data(), s->d_cand,
+      HIP_TRY(hipMemcpy(cands.data(), o.d_cand.get(),
                         sizeof(PostVrfCandidate) * take,
                         hipMemcpyDeviceToHost));
-      std::lock_guard<std::mutex> lk(s->nonce_mu);
-      for (unsigned int i = 0; i < take; i++) {
-        uint8_t lab[32];
-        for (int k = 0; k < 8; k++) {
-          uint32_t w = cands[i].label_be[k];
-          lab[4 * k] = (uint8_t)(w >> 24);
-          lab[4 * k + 1] = (uint8_t)(w >> 16);
-          lab[4 * k + 2] = (uint8_t)(w >> 8);
-          lab[4 * k + 3] = (uint8_t)w;
-        }
-        int c = std::memcmp(lab, cur_difficulty, 32);
-        if (!s->nonce_found || c < 0 ||
-            (c == 0 && cands[i].index < s->nonce_idx)) {
-          s->nonce_found = true;
-          s->nonce_idx = cands[i].index;
-          std::memcpy(s->nonce_label, lab, 32);
-          std::memcpy(cur_difficulty, lab, 32);
-          nonce_improved = true;
-        }
-      }
+      nonce_improved = merge_candidates(s, cands.data(), take, cur_difficulty);
     }
-    /* persist an improved running minimum immediately: metadata is the
-     * only carrier of the shard-local minimum across kill+resume (the
-     * creation-time write has no nonce yet, and a completed-at-exit-only
-     * write loses it on any interrupt — the cfg4 soak caught exactly
-     * that).  Improvements are rare (~log of batches), so this is a few
-     * small rewrites per session. */
-    if (nonce_improved && !s->data_dir.empty()) {
-      rc = write_metadata(s);
-      if (rc != POST_OK) return rc;
-    }
-
-    /* reference-label self-check (ErrReferenceLabelMismatch semantics,
-     * activation/post.go:299-312): compare the host label computed above */
-    if (ref_rc != 0) {
-      set_error("host reference label failed");
-      return POST_ERR;
-    }
-    if (do_selfcheck &&
-        std::memcmp(ref, s->h_batch + probe * POST_LABEL_SIZE,
-                    POST_LABEL_SIZE) != 0) {
-      set_error("reference label mismatch: device labels diverge from the "
-                "host reference (ErrReferenceLabelMismatch)");
-      return POST_ERR;
-    }
-
-    if (!s->data_dir.empty()) {
-      rc = write_batch_files(s, s->range_start + pos, count, s->h_batch);
-      if (rc != POST_OK) return rc;
-      if (s->seal_on) {
-        rc = seal_commit(s, 0, pos, count);
-        if (rc != POST_OK) return rc;
-      }
-    }
+    rc = finish_batch(s, o, sc, pos, count, nonce_improved, done);
+    if (rc != POST_OK) return rc;
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, s->ev0, s->ev1);
+    (void)hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get());
     s->last_kernel_ms += ms;
     pos += count;
-    s->written.store(pos);
-    *done += count;
   }
   return POST_OK;
 }
@@ -1474,68 +1401,34 @@ double post_init_last_kernel_ms(const PostInitSession *s) {
 /* nonce-only batch beyond the configured range (no label output) */
 static int nonce_only_batch(PostInitSession *s, uint64_t gstart,
                             uint64_t count) {
-  LabelKernelArgs args;
-  std::memset(&args, 0, sizeof(args));
-  load_commitment_words(s->commitment, args.commitment_le);
-  args.scrypt_n = s->cfg.scrypt_n;
-  args.gap_shift = s->gap_shift;
-  args.xbuf = s->d_xbuf;
-  args.scratch = s->d_scratch;
-  args.scratch_lanes = s->lanes;
+  OutputSet &o = s->set[0];
+  LabelKernelArgs args = init_label_args(s);
+  args.xbuf = s->d_xbuf.get();
   args.start = gstart;
   args.count = count;
   args.out = nullptr;
-  args.has_difficulty = 1;
-  args.cand = s->d_cand;
-  args.cand_count = s->d_cand_count;
-  args.cand_cap = s->cand_cap;
+  args.cand = o.d_cand.get();
+  args.cand_count = o.d_cand_count.get();
   uint8_t cur[32];
-  std::memset(cur, 0xff, 32);
-  {
-    std::lock_guard<std::mutex> lk(s->nonce_mu);
-    if (s->nonce_found) std::memcpy(cur, s->nonce_label, 32);
-  }
+  load_running_minimum(s, cur);
   difficulty_to_be_words(cur, args.difficulty_be);
   unsigned int zero = 0;
-  HIP_TRY(hipMemcpy(s->d_cand_count, &zero, sizeof(zero),
+  HIP_TRY(hipMemcpy(o.d_cand_count.get(), &zero, sizeof(zero),
                     hipMemcpyHostToDevice));
   HIP_TRY(poste_launch_label_kernel(&args, (uint32_t)(s->lanes / 64),
-                                    s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+                                    s->stream.get()));
+  HIP_TRY(hipStreamSynchronize(s->stream.get()));
   unsigned int n_cand = 0;
-  HIP_TRY(hipMemcpy(&n_cand, s->d_cand_count, sizeof(n_cand),
+  HIP_TRY(hipMemcpy(&n_cand, o.d_cand_count.get(), sizeof(n_cand),
                     hipMemcpyDeviceToHost));
   if (n_cand > 0) {
     unsigned int take = std::min(n_cand, s->cand_cap);
     std::vector<PostVrfCandidate> cands(take);
-    HIP_TRY(hipMemcpy(cands.data(), s->d_cand,
+    HIP_TRY(hipMemcpy(cands.data(), o.d_cand.get(),
                       sizeof(PostVrfCandidate) * take,
                       hipMemcpyDeviceToHost));
-    bool improved = false;
-    {
-      std::lock_guard<std::mutex> lk(s->nonce_mu);
-      for (unsigned int i = 0; i < take; i++) {
-        uint8_t lab[32];
-        for (int k = 0; k < 8; k++) {
-          uint32_t w = cands[i].label_be[k];
-          lab[4 * k] = (uint8_t)(w >> 24);
-          lab[4 * k + 1] = (uint8_t)(w >> 16);
-          lab[4 * k + 2] = (uint8_t)(w >> 8);
-          lab[4 * k + 3] = (uint8_t)w;
-        }
-        int c = s->nonce_found ? std::memcmp(lab, s->nonce_label, 32) : -1;
-        if (c < 0 || (c == 0 && cands[i].index < s->nonce_idx)) {
-          s->nonce_found = true;
-          s->nonce_idx = cands[i].index;
-          std::memcpy(s->nonce_label, lab, 32);
-          improved = true;
-        }
-      }
-    }
-    if (improved && !s->data_dir.empty()) {
-      int rc = write_metadata(s);
-      if (rc != POST_OK) return rc;
-    }
+    if (merge_candidates(s, cands.data(), take, cur) && !s->data_dir.empty())
+      return write_metadata(s);
   }
   return POST_OK;
 }
@@ -1587,7 +1480,7 @@ int post_init_copy_labels(const PostInitSession *s, uint64_t first,
     set_error("range out of bounds");
     return POST_ERR_INVALID_ARGS;
   }
-  HIP_TRY(hipMemcpy(out_host, s->d_all + first * POST_LABEL_SIZE,
+  HIP_TRY(hipMemcpy(out_host, s->d_all.get() + first * POST_LABEL_SIZE,
                     count * POST_LABEL_SIZE, hipMemcpyDeviceToHost));
   return POST_OK;
 }
@@ -1610,20 +1503,18 @@ int post_benchmark(uint32_t provider_id, uint32_t scrypt_n,
   cfg.scrypt_n = scrypt_n;
   cfg.provider_id = provider_id;
   cfg.scratch_bytes = 8ull << 30;
+  Event t0, t1;
+  HIP_TRY(t0.create());
+  HIP_TRY(t1.create());
   PostInitSession *s = nullptr;
   rc = post_init_new(&cfg, &s);
   if (rc != POST_OK) return rc;
-  hipEvent_t t0, t1;
-  (void)hipEventCreate(&t0);
-  (void)hipEventCreate(&t1);
-  (void)hipEventRecord(t0, nullptr);
+  (void)hipEventRecord(t0.get(), nullptr);
   rc = post_init_run(s);
-  (void)hipEventRecord(t1, nullptr);
-  (void)hipEventSynchronize(t1);
+  (void)hipEventRecord(t1.get(), nullptr);
+  (void)hipEventSynchronize(t1.get());
   float ms = 0;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
+  (void)hipEventElapsedTime(&ms, t0.get(), t1.get());
   if (rc == POST_OK && ms > 0)
     *labels_per_sec = (uint64_t)((double)cfg.labels_per_unit / (ms / 1e3));
   post_init_free(s);
@@ -1674,54 +1565,29 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
   if (seal) CHUNK = (CHUNK + SEAL_PAGE - 1) / SEAL_PAGE * SEAL_PAGE;
   const uint64_t chunk_lab = std::min(CHUNK, num_labels);
   const uint64_t chunk_pages = (chunk_lab + SEAL_PAGE - 1) / SEAL_PAGE;
-  uint8_t *d_labels[2] = {nullptr, nullptr};
-  uint8_t *h_labels[2] = {nullptr, nullptr};
-  uint8_t *d_dig[2] = {nullptr, nullptr};
-  uint8_t *h_dig[2] = {nullptr, nullptr};
-  hipStream_t stream = nullptr, seal_stream = nullptr;
-  hipEvent_t done[2] = {nullptr, nullptr};
-  hipEvent_t staged[2] = {nullptr, nullptr}, sealed[2] = {nullptr, nullptr};
-  auto cleanup = [&] {
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (seal_stream) (void)hipStreamSynchronize(seal_stream);
-    for (int p = 0; p < 2; p++) {
-      if (d_labels[p]) (void)hipFree(d_labels[p]);
-      if (h_labels[p]) (void)hipHostFree(h_labels[p]);
-      if (d_dig[p]) (void)hipFree(d_dig[p]);
-      if (h_dig[p]) (void)hipHostFree(h_dig[p]);
-      if (done[p]) (void)hipEventDestroy(done[p]);
-      if (staged[p]) (void)hipEventDestroy(staged[p]);
-      if (sealed[p]) (void)hipEventDestroy(sealed[p]);
-    }
-    if (stream) (void)hipStreamDestroy(stream);
-    if (seal_stream) (void)hipStreamDestroy(seal_stream);
-  };
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cleanup();                                                               \
-      return hip_fail(#expr, _e);                                              \
-    }                                                                          \
-  } while (0)
+  DevBuf<uint8_t> d_labels[2], d_dig[2];
+  PinnedBuf<uint8_t> h_labels[2], h_dig[2];
+  Event done[2], staged[2], sealed[2];
+  Stream main_stream, second_stream; /* last: synchronised, then the rest */
   for (int p = 0; p < 2; p++) {
-    HIP_TRY(hipMalloc(&d_labels[p], chunk_lab * 16));
-    HIP_TRY(hipHostMalloc(&h_labels[p], chunk_lab * 16));
-    HIP_TRY(hipEventCreate(&done[p]));
+    HIP_TRY(d_labels[p].alloc(chunk_lab * 16));
+    HIP_TRY(h_labels[p].alloc(chunk_lab * 16));
+    HIP_TRY(done[p].create());
     if (seal) {
-      HIP_TRY(hipMalloc(&d_dig[p], chunk_pages * SEAL_DIGEST));
-      HIP_TRY(hipHostMalloc(&h_dig[p], chunk_pages * SEAL_DIGEST));
+      HIP_TRY(d_dig[p].alloc(chunk_pages * SEAL_DIGEST));
+      HIP_TRY(h_dig[p].alloc(chunk_pages * SEAL_DIGEST));
     }
   }
-  HIP_TRY(hipStreamCreate(&stream));
+  HIP_TRY(main_stream.create());
   if (seal && seal_on_second_stream()) {
-    HIP_TRY(hipStreamCreate(&seal_stream));
+    HIP_TRY(second_stream.create());
     for (int p = 0; p < 2; p++) {
-      HIP_TRY(hipEventCreateWithFlags(&staged[p], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&sealed[p], hipEventDisableTiming));
+      HIP_TRY(staged[p].create(hipEventDisableTiming));
+      HIP_TRY(sealed[p].create(hipEventDisableTiming));
     }
   }
+  const hipStream_t stream = main_stream.get();
+  const hipStream_t seal_stream = second_stream.get();
 
   /* digests of the chunk in flight on each parity, not yet handed over */
   uint64_t pend_first[2] = {0, 0}, pend_pages[2] = {0, 0};
@@ -1729,7 +1595,7 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
     if (!pend_pages[p]) return POST_OK;
     const uint64_t n = pend_pages[p];
     pend_pages[p] = 0;
-    return (*seal)(pend_first[p], n, h_dig[p]);
+    return (*seal)(pend_first[p], n, h_dig[p].get());
   };
 
   int parity = 0;
@@ -1737,18 +1603,15 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
   for (uint64_t base = 0; base < num_labels; base += CHUNK, parity ^= 1) {
     uint64_t cnt = std::min(CHUNK, num_labels - base);
     /* wait until this parity's buffers are free, then stage the chunk */
-    if (inflight[parity]) HIP_TRY(hipEventSynchronize(done[parity]));
+    if (inflight[parity]) HIP_TRY(hipEventSynchronize(done[parity].get()));
     int rrc = seal ? hand_over(parity) : POST_OK;
-    if (rrc == POST_OK) rrc = read_labels(base, cnt, h_labels[parity]);
-    if (rrc != POST_OK) {
-      cleanup();
-      return rrc;
-    }
-    HIP_TRY(hipMemcpyAsync(d_labels[parity], h_labels[parity], cnt * 16,
-                           hipMemcpyHostToDevice, stream));
-    if (seal_stream) HIP_TRY(hipEventRecord(staged[parity], stream));
+    if (rrc == POST_OK) rrc = read_labels(base, cnt, h_labels[parity].get());
+    if (rrc != POST_OK) return rrc;
+    HIP_TRY(hipMemcpyAsync(d_labels[parity].get(), h_labels[parity].get(),
+                           cnt * 16, hipMemcpyHostToDevice, stream));
+    if (seal_stream) HIP_TRY(hipEventRecord(staged[parity].get(), stream));
     if (scan) {
-      scan->labels = (const uint4 *)d_labels[parity];
+      scan->labels = (const uint4 *)d_labels[parity].get();
       scan->count = cnt;
       scan->index_base = base;
       uint32_t blocks = (uint32_t)std::min<uint64_t>(
@@ -1759,22 +1622,23 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
       const uint64_t n_pages = (cnt + SEAL_PAGE - 1) / SEAL_PAGE;
       hipStream_t ss = seal_stream ? seal_stream : stream;
       SealKernelArgs ka;
-      ka.labels = (const uint4 *)d_labels[parity];
+      ka.labels = (const uint4 *)d_labels[parity].get();
       ka.count = cnt;
-      ka.digests = (uint4 *)d_dig[parity];
-      if (seal_stream) HIP_TRY(hipStreamWaitEvent(ss, staged[parity], 0));
+      ka.digests = (uint4 *)d_dig[parity].get();
+      if (seal_stream)
+        HIP_TRY(hipStreamWaitEvent(ss, staged[parity].get(), 0));
       HIP_TRY(poste_launch_seal_kernel(&ka, ss));
-      HIP_TRY(hipMemcpyAsync(h_dig[parity], d_dig[parity],
+      HIP_TRY(hipMemcpyAsync(h_dig[parity].get(), d_dig[parity].get(),
                              n_pages * SEAL_DIGEST, hipMemcpyDeviceToHost,
                              ss));
       if (seal_stream) {
-        HIP_TRY(hipEventRecord(sealed[parity], ss));
-        HIP_TRY(hipStreamWaitEvent(stream, sealed[parity], 0));
+        HIP_TRY(hipEventRecord(sealed[parity].get(), ss));
+        HIP_TRY(hipStreamWaitEvent(stream, sealed[parity].get(), 0));
       }
       pend_first[parity] = base / SEAL_PAGE;
       pend_pages[parity] = n_pages;
     }
-    HIP_TRY(hipEventRecord(done[parity], stream));
+    HIP_TRY(hipEventRecord(done[parity].get(), stream));
     inflight[parity] = true;
   }
   HIP_TRY(hipStreamSynchronize(stream));
@@ -1784,13 +1648,6 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
     rc = hand_over(parity);
     if (rc == POST_OK) rc = hand_over(parity ^ 1);
   }
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
-  } while (0)
-  cleanup();
   return rc;
 }
 
@@ -1838,77 +1695,50 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
     poste::prove_cipher_key(cfg->challenge, c, group_pow[grp], key);
     poste::aes128_expand(key, rk.data() + (size_t)c * 44);
   }
-  uint32_t *d_rk = nullptr;
-  HIP_TRY(hipMalloc(&d_rk, rk.size() * 4));
-  HIP_TRY(hipMemcpy(d_rk, rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
+  DevBuf<uint32_t> d_rk;
+  HIP_TRY(d_rk.alloc(rk.size() * 4));
+  HIP_TRY(hipMemcpy(d_rk.get(), rk.data(), rk.size() * 4,
+                    hipMemcpyHostToDevice));
 
   /* Expected total hits = nonces*k1 (a few thousand) regardless of label
    * count, so hits accumulate in one device buffer drained once at the
    * end of the pipeline. */
   const uint32_t HIT_CAP = 1u << 22;
-  PostScanHit *d_hits = nullptr;
-  unsigned int *d_hit_count = nullptr;
-  auto cleanup = [&] {
-    if (d_hits) (void)hipFree(d_hits);
-    if (d_hit_count) (void)hipFree(d_hit_count);
-    (void)hipFree(d_rk);
-  };
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cleanup();                                                               \
-      return hip_fail(#expr, _e);                                              \
-    }                                                                          \
-  } while (0)
-  HIP_TRY(hipMalloc(&d_hits, sizeof(PostScanHit) * HIT_CAP));
-  HIP_TRY(hipMalloc(&d_hit_count, 4));
+  DevBuf<PostScanHit> d_hits;
+  DevBuf<unsigned int> d_hit_count;
+  HIP_TRY(d_hits.alloc(sizeof(PostScanHit) * HIT_CAP));
+  HIP_TRY(d_hit_count.alloc(4));
   unsigned int zero = 0;
-  HIP_TRY(hipMemcpy(d_hit_count, &zero, 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_hit_count.get(), &zero, 4, hipMemcpyHostToDevice));
 
   ScanKernelArgs sa;
   std::memset(&sa, 0, sizeof(sa));
   sa.te = tbl.d_te;
   sa.sbox = tbl.d_sbox;
-  sa.rk = d_rk;
+  sa.rk = d_rk.get();
   sa.n_ciphers = n_ciphers;
   sa.difficulty = poste::proving_difficulty(cfg->k1, num_labels);
-  sa.hits = d_hits;
-  sa.hit_count = d_hit_count;
+  sa.hits = d_hits.get();
+  sa.hit_count = d_hit_count.get();
   sa.hit_cap = HIT_CAP;
 
   rc = label_pipeline(read_labels, num_labels, &sa, seal);
-  if (rc != POST_OK) {
-    cleanup();
-    return rc;
-  }
+  if (rc != POST_OK) return rc;
   unsigned int n_hits = 0;
-  HIP_TRY(hipMemcpy(&n_hits, d_hit_count, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&n_hits, d_hit_count.get(), 4, hipMemcpyDeviceToHost));
   if (n_hits > HIT_CAP) {
-    cleanup();
     set_error("scan hit buffer overflow (pathological K1/num_labels "
               "configuration)");
     return POST_ERR;
   }
   std::vector<PostScanHit> all_hits(n_hits);
   if (n_hits)
-    HIP_TRY(hipMemcpy(all_hits.data(), d_hits, sizeof(PostScanHit) * n_hits,
-                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(all_hits.data(), d_hits.get(),
+                      sizeof(PostScanHit) * n_hits, hipMemcpyDeviceToHost));
   if (hook) {
     rc = (*hook)(sa, all_hits);
-    if (rc != POST_OK) {
-      cleanup();
-      return rc;
-    }
+    if (rc != POST_OK) return rc;
   }
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
-  } while (0)
-  cleanup();
 
   /* winner: nonce whose k2-th smallest passing index is smallest
    * (streaming-order first across the ascending scan); tie -> lowest nonce */
@@ -1997,49 +1827,35 @@ int post_prove_scan(const uint8_t *labels, uint64_t count,
     poste::prove_cipher_key(cfg->challenge, c, group_pows[grp], key);
     poste::aes128_expand(key, rk.data() + (size_t)c * 44);
   }
-  uint32_t *d_rk = nullptr;
-  uint8_t *d_labels = nullptr;
-  PostScanHit *d_hits = nullptr;
-  unsigned int *d_hit_count = nullptr;
-  auto cleanup = [&] {
-    if (d_rk) (void)hipFree(d_rk);
-    if (d_labels) (void)hipFree(d_labels);
-    if (d_hits) (void)hipFree(d_hits);
-    if (d_hit_count) (void)hipFree(d_hit_count);
-  };
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cleanup();                                                               \
-      return hip_fail(#expr, _e);                                              \
-    }                                                                          \
-  } while (0)
-  HIP_TRY(hipMalloc(&d_rk, rk.size() * 4));
-  HIP_TRY(hipMemcpy(d_rk, rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
+  DevBuf<uint32_t> d_rk;
+  DevBuf<uint8_t> d_labels;
+  DevBuf<PostScanHit> d_hits;
+  DevBuf<unsigned int> d_hit_count;
+  HIP_TRY(d_rk.alloc(rk.size() * 4));
+  HIP_TRY(hipMemcpy(d_rk.get(), rk.data(), rk.size() * 4,
+                    hipMemcpyHostToDevice));
   const uint64_t CHUNK = prove_chunk_labels();
-  HIP_TRY(hipMalloc(&d_labels, std::min(CHUNK, count) * 16));
-  HIP_TRY(hipMalloc(&d_hits, sizeof(PostScanHit) * cap));
-  HIP_TRY(hipMalloc(&d_hit_count, 4));
+  HIP_TRY(d_labels.alloc(std::min(CHUNK, count) * 16));
+  HIP_TRY(d_hits.alloc(sizeof(PostScanHit) * cap));
+  HIP_TRY(d_hit_count.alloc(4));
   unsigned int zero = 0;
-  HIP_TRY(hipMemcpy(d_hit_count, &zero, 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_hit_count.get(), &zero, 4, hipMemcpyHostToDevice));
 
   ScanKernelArgs sa;
   std::memset(&sa, 0, sizeof(sa));
   sa.te = tbl.d_te;
   sa.sbox = tbl.d_sbox;
-  sa.rk = d_rk;
+  sa.rk = d_rk.get();
   sa.n_ciphers = n_ciphers;
   sa.difficulty = poste::proving_difficulty(cfg->k1, total_labels);
-  sa.hits = d_hits;
-  sa.hit_count = d_hit_count;
+  sa.hits = d_hits.get();
+  sa.hit_count = d_hit_count.get();
   sa.hit_cap = cap;
   for (uint64_t base = 0; base < count; base += CHUNK) {
     uint64_t cnt = std::min(CHUNK, count - base);
-    HIP_TRY(hipMemcpy(d_labels, labels + base * 16, cnt * 16,
+    HIP_TRY(hipMemcpy(d_labels.get(), labels + base * 16, cnt * 16,
                       hipMemcpyHostToDevice));
-    sa.labels = (const uint4 *)d_labels;
+    sa.labels = (const uint4 *)d_labels.get();
     sa.count = cnt;
     sa.index_base = index_base + base;
     uint32_t blocks = (uint32_t)std::min<uint64_t>(
@@ -2048,23 +1864,15 @@ int post_prove_scan(const uint8_t *labels, uint64_t count,
     HIP_TRY(hipDeviceSynchronize());
   }
   unsigned int got = 0;
-  HIP_TRY(hipMemcpy(&got, d_hit_count, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&got, d_hit_count.get(), 4, hipMemcpyDeviceToHost));
   if (got > cap) {
-    cleanup();
     set_error("scan hit buffer overflow (raise cap)");
     return POST_ERR;
   }
   std::vector<PostScanHit> tmp(got);
   if (got)
-    HIP_TRY(hipMemcpy(tmp.data(), d_hits, sizeof(PostScanHit) * got,
+    HIP_TRY(hipMemcpy(tmp.data(), d_hits.get(), sizeof(PostScanHit) * got,
                       hipMemcpyDeviceToHost));
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
-  } while (0)
-  cleanup();
   for (unsigned int i = 0; i < got; i++) {
     hits[i].index = tmp[i].index;
     hits[i].nonce = tmp[i].nonce;
@@ -2574,53 +2382,36 @@ static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
   const uint64_t batch = std::min<uint64_t>(windows, lanes * 4);
   const uint32_t blocks = (uint32_t)(lanes / 64); /* 64 quads/block */
 
-  uint32_t *d_scratch = nullptr, *d_xbuf = nullptr;
-  uint64_t *d_idx[2] = {nullptr, nullptr}, *h_idx[2] = {nullptr, nullptr};
-  uint8_t *d_exp[2] = {nullptr, nullptr}, *h_exp[2] = {nullptr, nullptr};
-  PostAuditMismatch *d_mis[2] = {nullptr, nullptr};
-  unsigned int *d_count[2] = {nullptr, nullptr};
-  unsigned int *h_count = nullptr; /* pinned, one per parity */
-  hipEvent_t done[2] = {nullptr, nullptr};
-  hipStream_t stream = nullptr, copy_stream = nullptr;
-  auto cleanup = [&] {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (int p = 0; p < 2; p++) {
-      if (d_idx[p]) (void)hipFree(d_idx[p]);
-      if (h_idx[p]) (void)hipHostFree(h_idx[p]);
-      if (d_exp[p]) (void)hipFree(d_exp[p]);
-      if (h_exp[p]) (void)hipHostFree(h_exp[p]);
-      if (d_mis[p]) (void)hipFree(d_mis[p]);
-      if (d_count[p]) (void)hipFree(d_count[p]);
-      if (done[p]) (void)hipEventDestroy(done[p]);
-    }
-    if (h_count) (void)hipHostFree(h_count);
-    if (d_scratch) (void)hipFree(d_scratch);
-    if (d_xbuf) (void)hipFree(d_xbuf);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
+  /* everything of the call, released before the "free" time is taken */
+  struct Res {
+    DevBuf<uint32_t> d_scratch, d_xbuf;
+    DevBuf<uint64_t> d_idx[2];
+    PinnedBuf<uint64_t> h_idx[2];
+    DevBuf<uint8_t> d_exp[2];
+    PinnedBuf<uint8_t> h_exp[2];
+    DevBuf<PostAuditMismatch> d_mis[2];
+    DevBuf<unsigned int> d_count[2];
+    PinnedBuf<unsigned int> h_count; /* one per parity */
+    Event done[2];
+    Stream stream, copy_stream; /* last: synchronised, then the rest */
   };
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cleanup();                                                               \
-      return hip_fail(#expr, _e);                                              \
-    }                                                                          \
-  } while (0)
-  HIP_TRY(hipStreamCreate(&stream));
-  HIP_TRY(hipStreamCreate(&copy_stream));
-  HIP_TRY(hipMalloc(&d_scratch, (size_t)lanes * per_lane));
-  HIP_TRY(hipMalloc(&d_xbuf, (size_t)batch * 128));
-  HIP_TRY(hipHostMalloc(&h_count, 2 * sizeof(unsigned int)));
+  std::optional<Res> res(std::in_place);
+  Res &r = *res;
+  HIP_TRY(r.stream.create());
+  HIP_TRY(r.copy_stream.create());
+  const hipStream_t stream = r.stream.get();
+  const hipStream_t copy_stream = r.copy_stream.get();
+  HIP_TRY(r.d_scratch.alloc((size_t)lanes * per_lane));
+  HIP_TRY(r.d_xbuf.alloc((size_t)batch * 128));
+  HIP_TRY(r.h_count.alloc(2 * sizeof(unsigned int)));
   for (int p = 0; p < 2; p++) {
-    HIP_TRY(hipMalloc(&d_idx[p], (size_t)batch * 8));
-    HIP_TRY(hipHostMalloc(&h_idx[p], (size_t)batch * 8));
-    HIP_TRY(hipMalloc(&d_exp[p], (size_t)batch * POST_LABEL_SIZE));
-    HIP_TRY(hipHostMalloc(&h_exp[p], (size_t)batch * POST_LABEL_SIZE));
-    HIP_TRY(hipMalloc(&d_mis[p], (size_t)batch * sizeof(PostAuditMismatch)));
-    HIP_TRY(hipMalloc(&d_count[p], sizeof(unsigned int)));
-    HIP_TRY(hipEventCreate(&done[p]));
+    HIP_TRY(r.d_idx[p].alloc((size_t)batch * 8));
+    HIP_TRY(r.h_idx[p].alloc((size_t)batch * 8));
+    HIP_TRY(r.d_exp[p].alloc((size_t)batch * POST_LABEL_SIZE));
+    HIP_TRY(r.h_exp[p].alloc((size_t)batch * POST_LABEL_SIZE));
+    HIP_TRY(r.d_mis[p].alloc((size_t)batch * sizeof(PostAuditMismatch)));
+    HIP_TRY(r.d_count[p].alloc(sizeof(unsigned int)));
+    HIP_TRY(r.done[p].create());
   }
 
   const double t_alloc = tick() - t_start;
@@ -2630,9 +2421,9 @@ static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
   load_commitment_words(commitment, aa.label.commitment_le);
   aa.label.scrypt_n = scrypt_n;
   aa.label.gap_shift = gap_shift;
-  aa.label.scratch = d_scratch;
+  aa.label.scratch = r.d_scratch.get();
   aa.label.scratch_lanes = lanes;
-  aa.label.xbuf = d_xbuf;
+  aa.label.xbuf = r.d_xbuf.get();
 
   std::vector<uint64_t> sample((size_t)batch);
   std::vector<PostAuditMismatch> mis;
@@ -2643,9 +2434,9 @@ static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
   auto drain = [&](int p) -> int {
     const uint32_t n = in_batch[p];
     if (n) {
-      hipError_t e = hipEventSynchronize(done[p]);
+      hipError_t e = hipEventSynchronize(r.done[p].get());
       if (e != hipSuccess) return hip_fail("hipEventSynchronize", e);
-      const unsigned int n_bad = h_count[p];
+      const unsigned int n_bad = r.h_count.get()[p];
       if (n_bad > n) {
         set_error("audit mismatch count exceeds the batch");
         return POST_ERR;
@@ -2653,7 +2444,7 @@ static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
       if (n_bad) {
         mis.resize(n_bad);
         /* its own stream: the next batch is already queued on `stream` */
-        e = hipMemcpyAsync(mis.data(), d_mis[p],
+        e = hipMemcpyAsync(mis.data(), r.d_mis[p].get(),
                            sizeof(PostAuditMismatch) * n_bad,
                            hipMemcpyDeviceToHost, copy_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(copy_stream);
@@ -2663,16 +2454,17 @@ static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
                     return x.index < y.index;
                   });
         for (unsigned int i = 0; i < n_bad && kept < cap; i++, kept++) {
+          const uint64_t *const idx = r.h_idx[p].get();
           const uint64_t *at =
-              std::lower_bound(h_idx[p], h_idx[p] + n, (uint64_t)mis[i].index);
-          if (at == h_idx[p] + n || *at != mis[i].index) {
+              std::lower_bound(idx, idx + n, (uint64_t)mis[i].index);
+          if (at == idx + n || *at != mis[i].index) {
             set_error("audit mismatch names an index outside its batch");
             return POST_ERR;
           }
           PostBadLabel &b = bad[kept];
           b.index = mis[i].index;
-          std::memcpy(b.on_disk, h_exp[p] + (size_t)(at - h_idx[p]) *
-                                               POST_LABEL_SIZE,
+          std::memcpy(b.on_disk,
+                      r.h_exp[p].get() + (size_t)(at - idx) * POST_LABEL_SIZE,
                       POST_LABEL_SIZE);
           std::memcpy(b.expected, mis[i].label, POST_LABEL_SIZE);
         }
@@ -2698,42 +2490,37 @@ static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
     rc = post_verify_data_sample(cfg->seed, cfg->sample_every, start, end, w,
                                  sample.data(), nw, &drawn);
     if (rc == POST_OK)
-      rc = gather(sample.data(), drawn, h_idx[parity], h_exp[parity],
-                  &present);
+      rc = gather(sample.data(), drawn, r.h_idx[parity].get(),
+                  r.h_exp[parity].get(), &present);
     t_gather += tick() - t0;
-    if (rc != POST_OK) {
-      cleanup();
-      return rc;
-    }
+    if (rc != POST_OK) return rc;
     report->labels_missing += drawn - present;
     in_batch[parity] = present;
     if (present) {
-      HIP_TRY(hipMemcpyAsync(d_idx[parity], h_idx[parity], (size_t)present * 8,
-                             hipMemcpyHostToDevice, stream));
-      HIP_TRY(hipMemcpyAsync(d_exp[parity], h_exp[parity],
+      HIP_TRY(hipMemcpyAsync(r.d_idx[parity].get(), r.h_idx[parity].get(),
+                             (size_t)present * 8, hipMemcpyHostToDevice,
+                             stream));
+      HIP_TRY(hipMemcpyAsync(r.d_exp[parity].get(), r.h_exp[parity].get(),
                              (size_t)present * POST_LABEL_SIZE,
                              hipMemcpyHostToDevice, stream));
-      HIP_TRY(hipMemsetAsync(d_count[parity], 0, sizeof(unsigned int),
-                             stream));
+      HIP_TRY(hipMemsetAsync(r.d_count[parity].get(), 0,
+                             sizeof(unsigned int), stream));
       aa.label.count = present;
-      aa.label.indices = d_idx[parity];
-      aa.expected = (const uint4 *)d_exp[parity];
-      aa.mismatch = d_mis[parity];
-      aa.count = d_count[parity];
+      aa.label.indices = r.d_idx[parity].get();
+      aa.expected = (const uint4 *)r.d_exp[parity].get();
+      aa.mismatch = r.d_mis[parity].get();
+      aa.count = r.d_count[parity].get();
       HIP_TRY(poste_launch_label_audit(&aa, blocks, stream));
-      HIP_TRY(hipMemcpyAsync(&h_count[parity], d_count[parity],
-                             sizeof(unsigned int), hipMemcpyDeviceToHost,
-                             stream));
-      HIP_TRY(hipEventRecord(done[parity], stream));
+      HIP_TRY(hipMemcpyAsync(r.h_count.get() + parity,
+                             r.d_count[parity].get(), sizeof(unsigned int),
+                             hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipEventRecord(r.done[parity].get(), stream));
     }
     if (have_prev) {
       t0 = tick();
       rc = drain(parity ^ 1);
       t_drain += tick() - t0;
-      if (rc != POST_OK) {
-        cleanup();
-        return rc;
-      }
+      if (rc != POST_OK) return rc;
     }
     have_prev = true;
     w += nw;
@@ -2744,13 +2531,7 @@ static int audit_core(const AuditGather &gather, const uint8_t commitment[32],
     t_drain += tick() - t0;
   }
   const double t_loop_end = tick();
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
-  } while (0)
-  cleanup();
+  res.reset();
   if (dbg)
     std::fprintf(stderr,
                  "[audit] lanes=%llu batch=%llu windows=%llu alloc %.3fs "
@@ -2960,7 +2741,7 @@ struct HealWork {
   std::vector<uint64_t> pages; /* bad pages, ascending */
   std::vector<uint8_t> want;   /* their sidecar digests */
   /* out */
-  uint8_t *d_labels = nullptr; /* compact buffer: page i at label 1024 i */
+  DevBuf<uint8_t> d_labels;    /* compact buffer: page i at label 1024 i */
   uint64_t count = 0;          /* its labels: (P - 1) 1024 + n_last */
   std::vector<uint8_t> labels; /* the same on the host */
   std::vector<bool> confirmed;
@@ -2969,9 +2750,6 @@ struct HealWork {
   uint64_t lanes = 0;
   double t_alloc = 0, t_regen = 0, t_digest = 0, t_rescan = 0, t_write = 0;
 
-  ~HealWork() {
-    if (d_labels) (void)hipFree(d_labels);
-  }
   uint64_t page_labels(size_t i) const {
     return std::min<uint64_t>(SEAL_PAGE, total - pages[i] * SEAL_PAGE);
   }
@@ -3050,33 +2828,22 @@ static int heal_regenerate(HealWork &w) {
   const uint32_t blocks = (uint32_t)(lanes / 64); /* 64 quads/block */
   w.lanes = lanes;
 
-  uint32_t *d_scratch = nullptr, *d_xbuf = nullptr;
-  uint64_t *d_idx = nullptr;
-  uint8_t *d_dig = nullptr;
-  auto cleanup = [&] {
-    (void)hipDeviceSynchronize();
-    if (d_scratch) (void)hipFree(d_scratch);
-    if (d_xbuf) (void)hipFree(d_xbuf);
-    if (d_idx) (void)hipFree(d_idx);
-    if (d_dig) (void)hipFree(d_dig);
-  };
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      cleanup();                                                               \
-      return hip_fail(#expr, _e);                                              \
-    }                                                                          \
-  } while (0)
+  DevBuf<uint32_t> d_scratch, d_xbuf;
+  DevBuf<uint64_t> d_idx;
+  DevBuf<uint8_t> d_dig;
+  /* the kernels run on the null stream: the device is idle before the
+   * buffers above go, on every way out */
+  struct DeviceSync {
+    ~DeviceSync() { (void)hipDeviceSynchronize(); }
+  } sync_first;
   double t0 = heal_tick();
-  HIP_TRY(hipMalloc(&d_scratch, (size_t)lanes * per_lane));
-  HIP_TRY(hipMalloc(&d_xbuf, (size_t)batch * 128));
-  HIP_TRY(hipMalloc(&d_idx, (size_t)count * 8));
-  HIP_TRY(hipMalloc(&d_dig, P * SEAL_DIGEST));
-  HIP_TRY(hipMalloc(&w.d_labels, (size_t)count * POST_LABEL_SIZE));
+  HIP_TRY(d_scratch.alloc((size_t)lanes * per_lane));
+  HIP_TRY(d_xbuf.alloc((size_t)batch * 128));
+  HIP_TRY(d_idx.alloc((size_t)count * 8));
+  HIP_TRY(d_dig.alloc(P * SEAL_DIGEST));
+  HIP_TRY(w.d_labels.alloc((size_t)count * POST_LABEL_SIZE));
   w.count = count;
-  HIP_TRY(hipMemcpy(d_idx, idx.data(), (size_t)count * 8,
+  HIP_TRY(hipMemcpy(d_idx.get(), idx.data(), (size_t)count * 8,
                     hipMemcpyHostToDevice));
   w.t_alloc = heal_tick() - t0;
 
@@ -3088,14 +2855,14 @@ static int heal_regenerate(HealWork &w) {
   load_commitment_words(commitment, la.commitment_le);
   la.scrypt_n = scrypt_n;
   la.gap_shift = gap_shift;
-  la.scratch = d_scratch;
+  la.scratch = d_scratch.get();
   la.scratch_lanes = lanes;
-  la.xbuf = d_xbuf;
+  la.xbuf = d_xbuf.get();
   /* the batches share scratch and xbuf: back to back on one stream */
   for (uint64_t off = 0; off < count; off += batch) {
     la.count = std::min(batch, count - off);
-    la.indices = d_idx + off;
-    la.out = w.d_labels + off * POST_LABEL_SIZE;
+    la.indices = d_idx.get() + off;
+    la.out = w.d_labels.get() + off * POST_LABEL_SIZE;
     HIP_TRY(poste_launch_label_kernel(&la, blocks, nullptr));
   }
   HIP_TRY(hipDeviceSynchronize());
@@ -3103,23 +2870,17 @@ static int heal_regenerate(HealWork &w) {
 
   t0 = heal_tick();
   SealKernelArgs ka;
-  ka.labels = (const uint4 *)w.d_labels;
+  ka.labels = (const uint4 *)w.d_labels.get();
   ka.count = count;
-  ka.digests = (uint4 *)d_dig;
+  ka.digests = (uint4 *)d_dig.get();
   std::vector<uint8_t> got(P * SEAL_DIGEST);
   HIP_TRY(poste_launch_seal_kernel(&ka, nullptr));
-  HIP_TRY(hipMemcpy(got.data(), d_dig, got.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(got.data(), d_dig.get(), got.size(),
+                    hipMemcpyDeviceToHost));
   w.t_digest = heal_tick() - t0;
   w.labels.resize((size_t)count * POST_LABEL_SIZE);
-  HIP_TRY(hipMemcpy(w.labels.data(), w.d_labels, w.labels.size(),
+  HIP_TRY(hipMemcpy(w.labels.data(), w.d_labels.get(), w.labels.size(),
                     hipMemcpyDeviceToHost));
-#undef HIP_TRY
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) return hip_fail(#expr, _e);                          \
-  } while (0)
-  cleanup();
 
   w.confirmed.assign(P, false);
   const LabelReader read = dir_reader(*w.files);
@@ -3149,7 +2910,7 @@ static int heal_rescan(HealWork &w, const ScanKernelArgs &pass,
                        std::vector<PostScanHit> &hits) {
   const double t0 = heal_tick();
   ScanKernelArgs sa = pass;
-  sa.labels = (const uint4 *)w.d_labels;
+  sa.labels = (const uint4 *)w.d_labels.get();
   sa.count = w.count;
   sa.index_base = 0;
   HIP_TRY(hipMemset(sa.hit_count, 0, 4));
@@ -3604,43 +3365,36 @@ int post_seal_digest_stream(const uint8_t *labels, uint64_t count,
   int rc = require_gpu(provider_id);
   if (rc != POST_OK) return rc;
 
-  struct Bufs {
-    uint4 *labels = nullptr, *dig = nullptr;
-    SealCarry *carry = nullptr;
-    ~Bufs() {
-      if (labels) (void)hipFree(labels);
-      if (dig) (void)hipFree(dig);
-      if (carry) (void)hipFree(carry);
-    }
-  } d;
+  DevBuf<uint4> d_labels, d_dig;
+  DevBuf<SealCarry> d_carry;
   const uint64_t all_pages = seal_pages(count);
-  HIP_TRY(hipMalloc(&d.labels, (size_t)count * 16));
-  HIP_TRY(hipMalloc(&d.dig, (size_t)(all_pages * SEAL_DIGEST)));
-  HIP_TRY(hipMalloc(&d.carry, 2 * sizeof(SealCarry)));
-  HIP_TRY(hipMemcpy(d.labels, labels, (size_t)count * 16,
+  HIP_TRY(d_labels.alloc((size_t)count * 16));
+  HIP_TRY(d_dig.alloc((size_t)(all_pages * SEAL_DIGEST)));
+  HIP_TRY(d_carry.alloc(2 * sizeof(SealCarry)));
+  HIP_TRY(hipMemcpy(d_labels.get(), labels, (size_t)count * 16,
                     hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d.dig, 0, (size_t)(all_pages * SEAL_DIGEST)));
-  HIP_TRY(hipMemset(d.carry, 0, 2 * sizeof(SealCarry)));
+  HIP_TRY(hipMemset(d_dig.get(), 0, (size_t)(all_pages * SEAL_DIGEST)));
+  HIP_TRY(hipMemset(d_carry.get(), 0, 2 * sizeof(SealCarry)));
   uint64_t launches = 0, at = 0;
   for (uint32_t i = 0; i <= n_cuts; i++) {
     const uint64_t to = i < n_cuts ? cuts[i] : count;
     if (to == at) continue;
     SealStreamArgs a;
-    a.labels = d.labels + at;
+    a.labels = d_labels.get() + at;
     a.g0 = first_index + at;
     a.count = to - at;
     a.stream_end = stream_end ? first_index + count : UINT64_MAX;
-    a.carry_in = d.carry + (launches & 1);
-    a.carry_out = d.carry + ((launches + 1) & 1);
+    a.carry_in = d_carry.get() + (launches & 1);
+    a.carry_out = d_carry.get() + ((launches + 1) & 1);
     /* lane l of the segment is page at / 1024 + l of the buffer */
-    a.digests = d.dig + at / SEAL_PAGE;
+    a.digests = d_dig.get() + at / SEAL_PAGE;
     HIP_TRY(poste_launch_seal_stream_kernel(&a, nullptr));
     launches++;
     at = to;
   }
   HIP_TRY(hipDeviceSynchronize());
   if (out_pages)
-    HIP_TRY(hipMemcpy(digests, d.dig, (size_t)(out_pages * SEAL_DIGEST),
+    HIP_TRY(hipMemcpy(digests, d_dig.get(), (size_t)(out_pages * SEAL_DIGEST),
                       hipMemcpyDeviceToHost));
   *n_pages = out_pages;
   return POST_OK;
@@ -3854,25 +3608,25 @@ int post_verify_batch_seeded(const PostProof *proofs,
                    tick() - t0, tasks.size(), (unsigned long long)lanes);
       t0 = tick();
     }
-    HIP_TRY(hipMemcpy(ws->d_idx, h_idx.data(), h_idx.size() * 8,
+    HIP_TRY(hipMemcpy(ws->d_idx.get(), h_idx.data(), h_idx.size() * 8,
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->d_cid, h_cid.data(), h_cid.size() * 4,
+    HIP_TRY(hipMemcpy(ws->d_cid.get(), h_cid.data(), h_cid.size() * 4,
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->d_cm, commit_words.data(),
+    HIP_TRY(hipMemcpy(ws->d_cm.get(), commit_words.data(),
                       commit_words.size() * 4, hipMemcpyHostToDevice));
 
     LabelKernelArgs la;
     std::memset(&la, 0, sizeof(la));
     la.scrypt_n = cfg->scrypt_n;
     la.gap_shift = gap_shift;
-    la.xbuf = ws->d_xbuf;
+    la.xbuf = ws->d_xbuf.get();
     la.out_full = 1;
-    la.scratch = ws->d_scratch;
+    la.scratch = ws->d_scratch.get();
     la.scratch_lanes = lanes;
-    la.out = ws->d_out;
-    la.indices = h_idx.size() ? ws->d_idx : nullptr;
-    la.commit_ids = ws->d_cid;
-    la.commitments = ws->d_cm;
+    la.out = ws->d_out.get();
+    la.indices = h_idx.size() ? ws->d_idx.get() : nullptr;
+    la.commit_ids = ws->d_cid.get();
+    la.commitments = ws->d_cm.get();
     la.count = tasks.size();
     if (dbg) {
       std::fprintf(stderr, "[verify] h2d %.3fs\n", tick() - t0);
@@ -3889,23 +3643,23 @@ int post_verify_batch_seeded(const PostProof *proofs,
     /* device-side AES threshold predicate over the recomputed labels */
     rc = ws_reserve_proofs(ws, n);
     if (rc != POST_OK) return rc;
-    HIP_TRY(hipMemcpy(ws->d_vrk, vrk.data(), vrk.size() * 4,
+    HIP_TRY(hipMemcpy(ws->d_vrk.get(), vrk.data(), vrk.size() * 4,
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->d_half, vhalf.data(), vhalf.size(),
+    HIP_TRY(hipMemcpy(ws->d_half.get(), vhalf.data(), vhalf.size(),
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->d_vdiff, vdiff.data(), vdiff.size() * 8,
+    HIP_TRY(hipMemcpy(ws->d_vdiff.get(), vdiff.data(), vdiff.size() * 8,
                       hipMemcpyHostToDevice));
     VerifyPredArgs pa;
     std::memset(&pa, 0, sizeof(pa));
-    pa.labels2 = (const uint4 *)ws->d_out;
+    pa.labels2 = (const uint4 *)ws->d_out.get();
     pa.count = tasks.size();
     pa.te = tbl.d_te;
     pa.sbox = tbl.d_sbox;
-    pa.rk = ws->d_vrk;
-    pa.task_proof = ws->d_cid; /* task->proof map doubles as commit id */
-    pa.half = ws->d_half;
-    pa.difficulty = ws->d_vdiff;
-    pa.pass = ws->d_pass;
+    pa.rk = ws->d_vrk.get();
+    pa.task_proof = ws->d_cid.get(); /* task->proof map doubles as commit id */
+    pa.half = ws->d_half.get();
+    pa.difficulty = ws->d_vdiff.get();
+    pa.pass = ws->d_pass.get();
     uint32_t pblocks = (uint32_t)std::min<uint64_t>(
         (tasks.size() + THREADS - 1) / THREADS, VERIFY_PRED_MAX_BLOCKS);
     HIP_TRY(poste_launch_verify_pred_kernel(&pa, pblocks, nullptr));
@@ -3914,7 +3668,7 @@ int post_verify_batch_seeded(const PostProof *proofs,
       std::fprintf(stderr, "[verify] predicate %.3fs\n", tick() - t0);
       t0 = tick();
     }
-    HIP_TRY(hipMemcpy(h_pass.data(), ws->d_pass, h_pass.size(),
+    HIP_TRY(hipMemcpy(h_pass.data(), ws->d_pass.get(), h_pass.size(),
                       hipMemcpyDeviceToHost));
   }
 
@@ -3952,35 +3706,30 @@ int post_verify_vrf_nonce(const PostProofMetadata *meta, uint64_t index,
 
   uint32_t gap_shift = pick_gap_shift(scrypt_n);
   uint64_t per_lane = ((uint64_t)scrypt_n >> gap_shift) * 128;
-  uint32_t *d_scratch = nullptr;
-  uint64_t *d_idx = nullptr;
-  uint8_t *d_out = nullptr;
-  uint32_t *d_xbuf1 = nullptr;
-  HIP_TRY(hipMalloc(&d_scratch, (size_t)128 * per_lane));
-  HIP_TRY(hipMalloc(&d_idx, 8));
-  HIP_TRY(hipMalloc(&d_out, 32));
-  HIP_TRY(hipMalloc(&d_xbuf1, 128));
-  HIP_TRY(hipMemcpy(d_idx, &index, 8, hipMemcpyHostToDevice));
+  DevBuf<uint32_t> d_scratch, d_xbuf1;
+  DevBuf<uint64_t> d_idx;
+  DevBuf<uint8_t> d_out;
+  HIP_TRY(d_scratch.alloc((size_t)128 * per_lane));
+  HIP_TRY(d_idx.alloc(8));
+  HIP_TRY(d_out.alloc(32));
+  HIP_TRY(d_xbuf1.alloc(128));
+  HIP_TRY(hipMemcpy(d_idx.get(), &index, 8, hipMemcpyHostToDevice));
   LabelKernelArgs la;
   std::memset(&la, 0, sizeof(la));
   load_commitment_words(cm, la.commitment_le);
   la.scrypt_n = scrypt_n;
   la.gap_shift = gap_shift;
-  la.xbuf = d_xbuf1;
+  la.xbuf = d_xbuf1.get();
   la.out_full = 1;
-  la.scratch = d_scratch;
+  la.scratch = d_scratch.get();
   la.scratch_lanes = 128;
-  la.out = d_out;
-  la.indices = d_idx;
+  la.out = d_out.get();
+  la.indices = d_idx.get();
   la.count = 1;
   HIP_TRY(poste_launch_label_kernel(&la, 1, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   uint8_t full[32];
-  HIP_TRY(hipMemcpy(full, d_out, 32, hipMemcpyDeviceToHost));
-  (void)hipFree(d_scratch);
-  (void)hipFree(d_idx);
-  (void)hipFree(d_out);
-  (void)hipFree(d_xbuf1);
+  HIP_TRY(hipMemcpy(full, d_out.get(), 32, hipMemcpyDeviceToHost));
   uint8_t difficulty[32];
   poste::vrf_difficulty(num_labels, difficulty);
   if (std::memcmp(full, difficulty, 32) < 0) return POST_OK;
@@ -4032,48 +3781,42 @@ int post_selftest_verify_pred(const uint8_t *labels, uint64_t count,
   rc = get_aes_tables((int)provider_id, tbl);
   if (rc != POST_OK) return rc;
 
-  struct Bufs {
-    uint8_t *labels = nullptr, *half = nullptr, *pass = nullptr;
-    uint32_t *rk = nullptr, *task_proof = nullptr;
-    uint64_t *diff = nullptr;
-    ~Bufs() {
-      (void)hipFree(labels); (void)hipFree(half); (void)hipFree(pass);
-      (void)hipFree(rk); (void)hipFree(task_proof); (void)hipFree(diff);
-    }
-  } d;
-  HIP_TRY(hipMalloc(&d.labels, (size_t)count * 32));
-  HIP_TRY(hipMalloc(&d.task_proof, (size_t)count * 4));
-  HIP_TRY(hipMalloc(&d.pass, (size_t)count));
-  HIP_TRY(hipMalloc(&d.rk, rk.size() * 4));
-  HIP_TRY(hipMalloc(&d.half, n_proofs));
-  HIP_TRY(hipMalloc(&d.diff, (size_t)n_proofs * 8));
-  HIP_TRY(hipMemcpy(d.labels, labels, (size_t)count * 32,
+  DevBuf<uint8_t> d_labels, d_half, d_pass;
+  DevBuf<uint32_t> d_rk, d_task_proof;
+  DevBuf<uint64_t> d_diff;
+  HIP_TRY(d_labels.alloc((size_t)count * 32));
+  HIP_TRY(d_task_proof.alloc((size_t)count * 4));
+  HIP_TRY(d_pass.alloc((size_t)count));
+  HIP_TRY(d_rk.alloc(rk.size() * 4));
+  HIP_TRY(d_half.alloc(n_proofs));
+  HIP_TRY(d_diff.alloc((size_t)n_proofs * 8));
+  HIP_TRY(hipMemcpy(d_labels.get(), labels, (size_t)count * 32,
                     hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.task_proof, task_proof, (size_t)count * 4,
+  HIP_TRY(hipMemcpy(d_task_proof.get(), task_proof, (size_t)count * 4,
                     hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d.pass, 0xEE, (size_t)count)); /* neither verdict */
-  HIP_TRY(hipMemcpy(d.rk, rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.half, halves, n_proofs, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.diff, difficulties, (size_t)n_proofs * 8,
+  HIP_TRY(hipMemset(d_pass.get(), 0xEE, (size_t)count)); /* neither verdict */
+  HIP_TRY(hipMemcpy(d_rk.get(), rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_half.get(), halves, n_proofs, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_diff.get(), difficulties, (size_t)n_proofs * 8,
                     hipMemcpyHostToDevice));
 
   VerifyPredArgs pa;
   std::memset(&pa, 0, sizeof(pa));
-  pa.labels2 = (const uint4 *)d.labels;
+  pa.labels2 = (const uint4 *)d_labels.get();
   pa.count = count;
   pa.te = tbl.d_te;
   pa.sbox = tbl.d_sbox;
-  pa.rk = d.rk;
-  pa.task_proof = d.task_proof;
-  pa.half = d.half;
-  pa.difficulty = d.diff;
-  pa.pass = d.pass;
+  pa.rk = d_rk.get();
+  pa.task_proof = d_task_proof.get();
+  pa.half = d_half.get();
+  pa.difficulty = d_diff.get();
+  pa.pass = d_pass.get();
   uint32_t pblocks = (uint32_t)std::min<uint64_t>(
       (count + THREADS - 1) / THREADS,
       max_blocks ? max_blocks : VERIFY_PRED_MAX_BLOCKS);
   HIP_TRY(poste_launch_verify_pred_kernel(&pa, pblocks, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(pass, d.pass, (size_t)count, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(pass, d_pass.get(), (size_t)count, hipMemcpyDeviceToHost));
   return POST_OK;
 }
 

@@ -233,3 +233,20 @@ def test_arms_give_identical_bytes():
         got, nonces = run_arm(mode, steps, scratch, start)
         assert got == want, mode
         assert nonces == wn, mode
+
+
+@gpu
+def test_monolithic_uneven_steps_match_oracle_and_default():
+    """POST_ROMIX_MIX=0, the monolithic kernel, which shares the host half
+    of a batch (candidate merge, self-check, bookkeeping) with the split
+    path.  Three uneven calls from a non-zero start: a full batch of 512
+    and a part of one, less than a workgroup, and a ragged 3 * 128 + 37.
+    Labels and the nonce after every call against the oracle, and the
+    default arm gives the same over the same range."""
+    steps, start = (512 + 192, 65, 3 * 128 + 37), THREE_UNIT_START
+    want, _, _ = oracle_range(start, sum(steps), N)
+    wn = want_nonces(steps, start)
+    for mode in ("0", None):
+        got, nonces = run_arm(mode, steps, SLOTS128, start)
+        assert got == want, mode
+        assert nonces == wn, mode
