@@ -13,7 +13,7 @@ all: $(ENGINE) oracle
 SRCS_ENGINE := $(CSRC)/kernels.hip $(CSRC)/engine.cpp $(CSRC)/crypto_host.cpp
 HDRS_ENGINE := $(CSRC)/post_common.h $(CSRC)/kernel_args.h \
                $(CSRC)/crypto_host.h $(CSRC)/hip_owned.h \
-               include/spacemesh_post.h
+               $(CSRC)/init_proof_host.h include/spacemesh_post.h
 
 $(ENGINE): $(SRCS_ENGINE) $(HDRS_ENGINE)
 	$(HIPCC) $(HIPFLAGS) -shared $(SRCS_ENGINE) -o $@
@@ -47,11 +47,24 @@ hip_owned_test: tools/hip_owned_test
 	./tools/hip_owned_test
 .PHONY: hip_owned_test
 
+# Host check of the initial proof's part files (csrc/init_proof_host.h: parse,
+# truncate, merge, tiling, winner) under ASan + UBSan: a stand-alone program,
+# no GPU and no HIP.  DIR holds postdata_hits.part-* files, TOTAL is the dir's
+# label count.  Not part of `all`.
+tools/init_proof_host_test: tools/init_proof_host_test.cpp \
+    $(CSRC)/init_proof_host.h $(CSRC)/crypto_host.cpp $(CSRC)/crypto_host.h
+	$(CXX) -O1 -g -std=c++17 -Wall -pthread -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined tools/init_proof_host_test.cpp \
+	    $(CSRC)/crypto_host.cpp -o $@
+init_proof_host_test: tools/init_proof_host_test
+	./tools/init_proof_host_test $(DIR) $(TOTAL)
+.PHONY: init_proof_host_test
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(ENGINE) tools/hip_owned_test
+	rm -f $(ENGINE) tools/hip_owned_test tools/init_proof_host_test
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

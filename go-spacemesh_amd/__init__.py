@@ -23,6 +23,8 @@ from .api import (  # noqa: F401
     EngineError,
     HealOpts,
     HealReport,
+    InitProofReport,
+    InitialProofOpts,
     PostConfig,
     PostProof,
     PostProofMetadata,
@@ -33,6 +35,7 @@ from .api import (  # noqa: F401
     SealReport,
     VerifyOpts,
     check_seal,
+    init_proof_assemble,
     load_engine,
     prove_checked,
     prove_healed,
@@ -50,6 +53,7 @@ __all__ = [
     "AuditOpts", "AuditReport", "BatchingVerifier", "Engine", "EngineError", "HealOpts", "HealReport", "OffloadingVerifier", "PostConfig", "PostProof",
     "PostProofMetadata", "PostSetupManager", "PostSetupOpts", "PostVerifier",
     "ProveOpts", "SealReport", "VerifyOpts", "check_seal", "events",
+    "InitProofReport", "InitialProofOpts", "init_proof_assemble",
     "load_engine", "prove_checked", "prove_healed", "repair_data",
     "sample_indices", "seal_assemble", "seal_data",
     "seal_digest_buffer", "seal_digest_stream", "verify_data",

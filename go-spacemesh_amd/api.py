@@ -139,6 +139,12 @@ class _CHealReport(ctypes.Structure):
                 ("reserved", c_uint32)]
 
 
+class _CInitProofReport(ctypes.Structure):
+    _fields_ = [("total_labels", c_uint64), ("labels_covered", c_uint64),
+                ("hits", c_uint64), ("parts", c_uint32),
+                ("reserved", c_uint32)]
+
+
 _AUDIT_PROGRESS = ctypes.CFUNCTYPE(c_int, c_void_p, c_uint64, c_uint64)
 
 _lib_lock = threading.Lock()
@@ -214,6 +220,10 @@ def load_engine() -> ctypes.CDLL:
                                        POINTER(_CSealReport)]),
             "post_init_enable_seal": (c_int, [c_void_p]),
             "post_seal_assemble": (c_int, [c_char_p, POINTER(c_uint64)]),
+            "post_init_enable_proof": (c_int, [c_void_p,
+                                               POINTER(_CProveConfig)]),
+            "post_init_proof_assemble": (c_int, [
+                c_char_p, POINTER(CProof), POINTER(_CInitProofReport)]),
             "post_seal_digest_stream": (c_int, [
                 ctypes.c_char_p, c_uint64, c_uint64, POINTER(c_uint64),
                 c_uint32, c_uint32, c_uint32, ctypes.c_char_p, c_uint64,
@@ -268,6 +278,38 @@ class PostConfig:
 
 
 @dataclasses.dataclass
+class InitialProofOpts:
+    """The initial proof found during init: the proving
+    parameters of ProveOpts together with those of PostConfig that a proof
+    needs, since they must be known when the session is created.  The
+    challenge is shared.ZeroChallenge unless a caller knows better."""
+    k1: int = 26
+    k2: int = 37
+    pow_difficulty: bytes = PostConfig.pow_difficulty
+    pow_mode: int = POW_MODE_BLAKE3
+    nonces: int = 288
+    threads: int = 0
+    challenge: bytes = bytes(32)
+
+    @classmethod
+    def of(cls, cfg: "PostConfig", opts: "Optional[ProveOpts]" = None,
+           challenge: bytes = bytes(32)) -> "InitialProofOpts":
+        opts = opts or ProveOpts()
+        return cls(k1=cfg.k1, k2=cfg.k2, pow_difficulty=cfg.pow_difficulty,
+                   pow_mode=cfg.pow_mode, nonces=opts.nonces,
+                   threads=opts.threads, challenge=challenge)
+
+    def to_c(self) -> _CProveConfig:
+        pc = _CProveConfig()
+        ctypes.memmove(pc.challenge, self.challenge, 32)
+        pc.k1, pc.k2, pc.nonces = self.k1, self.k2, self.nonces
+        ctypes.memmove(pc.pow_difficulty, self.pow_difficulty, 32)
+        pc.pow_mode = self.pow_mode
+        pc.pow_threads = self.threads
+        return pc
+
+
+@dataclasses.dataclass
 class PostSetupOpts:
     """Mirror of activation/post.go:52-61 PostSetupOpts."""
     data_dir: Optional[str] = None
@@ -278,6 +320,8 @@ class PostSetupOpts:
     index_start: int = 0                # shard range
     index_end: int = 0
     scratch_bytes: int = 0
+    # scan for the initial proof during init
+    initial_proof: Optional[InitialProofOpts] = None
     seal: bool = False                  # seal during init
 
 
@@ -465,6 +509,13 @@ class PostSetupManager:
         self._session = handle
         if self.opts.seal:
             rc = self.engine.lib.post_init_enable_seal(handle)
+            if rc != 0:
+                err = self.engine.lib.post_last_error().decode()
+                self.reset()
+                raise EngineError(rc, err)
+        if self.opts.initial_proof is not None:
+            pc = self.opts.initial_proof.to_c()
+            rc = self.engine.lib.post_init_enable_proof(handle, byref(pc))
             if rc != 0:
                 err = self.engine.lib.post_last_error().decode()
                 self.reset()
@@ -660,6 +711,32 @@ def seal_assemble(data_dir: str) -> int:
     pages = c_uint64(0)
     eng._check(eng.lib.post_seal_assemble(data_dir.encode(), byref(pages)))
     return pages.value
+
+
+@dataclasses.dataclass
+class InitProofReport:
+    """What init_proof_assemble merged."""
+    total_labels: int
+    labels_covered: int
+    hits: int
+    parts: int
+
+
+def init_proof_assemble(data_dir: str) -> tuple:
+    """The initial proof of a dir whose init ran with the scan on, from its
+    postdata_hits.part-* files: (proof, report).  Host only, reads only.
+    EngineError(IO) names the first missing index range while a shard is
+    unfinished; EngineError(NO_NONCE) when no nonce reaches K2."""
+    eng = Engine()
+    out = CProof()
+    rep = _CInitProofReport()
+    eng._check(eng.lib.post_init_proof_assemble(data_dir.encode(), byref(out),
+                                                byref(rep)))
+    proof = PostProof(nonce=out.nonce,
+                      indices=bytes(out.indices[:out.indices_len]),
+                      pow=out.pow)
+    return proof, InitProofReport(rep.total_labels, rep.labels_covered,
+                                  rep.hits, rep.parts)
 
 
 def seal_data(data_dir: str, provider_id: int = 0) -> SealReport:

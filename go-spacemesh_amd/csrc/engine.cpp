@@ -38,6 +38,7 @@
 
 #include "crypto_host.h"
 #include "hip_owned.h"
+#include "init_proof_host.h"
 #include "kernel_args.h"
 #include "post_common.h"
 
@@ -281,6 +282,13 @@ struct OutputSet {
   PinnedBuf<uint8_t> h_seal_dig;
   /* POST_SEAL_DEBUG: the stream kernel timed per batch, printed at the end */
   Event ev_seal[2];
+  /* initial proof during init: the batch's hits, its count, and what the
+   * host gets of both in front of ev_done */
+  DevBuf<PostScanHit> d_hits;
+  DevBuf<unsigned int> d_hit_count;
+  PinnedBuf<PostScanHit> h_hits; /* PROOF_HIT_WINDOW records */
+  PinnedBuf<unsigned int> h_hit_count;
+  Event ev_scan[2];              /* POST_INIT_PROOF_DEBUG */
 };
 
 struct PostInitSession {
@@ -335,6 +343,22 @@ struct PostInitSession {
   double seal_ms = 0, seal_ms_max = 0;
   uint64_t seal_timed = 0;
 
+  /* initial proof during init (post_init_enable_proof); all
+   * unused and nothing of it queued while proof_on is false */
+  bool proof_on = false;
+  int proof_fd = -1;          /* the part file */
+  initproof::Header proof_hdr;
+  uint64_t proof_pos = 0;     /* relative position of the part's last marker;
+                                 UINT64_MAX while an append is under way */
+  uint64_t proof_bytes = 0;   /* size of the part file */
+  int proof_variant = 0;      /* POSTE_SCAN_RESIDENT_* */
+  uint32_t proof_blocks = 0;  /* grid cap */
+  uint32_t proof_hit_cap = 0; /* records per output set */
+  ScanKernelArgs proof_scan;  /* tables, round keys, difficulty */
+  DevBuf<uint32_t> d_proof_rk;
+  double proof_ms = 0, proof_ms_max = 0;
+  uint64_t proof_timed = 0, proof_hits = 0, proof_refetch = 0;
+
   /* declared last, so destroyed first (hip_owned.h) */
   Stream stream, stream_b, stream_c, copy_stream;
 
@@ -347,6 +371,7 @@ struct PostInitSession {
   ~PostInitSession() {
     sync_streams(); /* they wait on each other's events: all, then release */
     if (seal_fd >= 0) (void)::close(seal_fd);
+    if (proof_fd >= 0) (void)::close(proof_fd);
   }
 };
 
@@ -975,6 +1000,339 @@ int post_init_enable_seal(PostInitSession *s) {
   return POST_OK;
 }
 
+/* ------------------- initial proof during init -------------------
+ *
+ * DESIGN 3.8.  The session runs the proving scan over every batch where the
+ * tail kernel left it and appends the hits to postdata_hits.part-<index_start>
+ * (format, parser and resume: init_proof_host.h) once the batch's labels are
+ * in the files.  All of it hangs off proof_on: a session that never called
+ * post_init_enable_proof queues and waits for exactly what it did before. */
+
+/* records of a batch the host gets with the count, in front of ev_done (16
+ * KiB): a mainnet batch expects about 0.2 hits, so more is fetched next to
+ * never.  Fetching more is a blocking copy behind everything queued, the next
+ * batch included, so it empties the pipeline once: at 64 records a 2^24-label
+ * space with 288 nonces (234 hits a batch) paid that on every batch, 4 % of
+ * the run (profiles/init_proof.md). */
+constexpr uint32_t PROOF_HIT_WINDOW = 1024;
+constexpr uint64_t PROOF_HIT_CAP_MIN = 4096, PROOF_HIT_CAP_MAX = 1u << 16;
+
+/* device records per batch: 16 times the expectation, within the bounds */
+static uint32_t proof_hit_capacity(uint64_t batch, uint32_t nonces,
+                                   uint32_t k1, uint64_t total) {
+  const unsigned __int128 num = (unsigned __int128)batch * nonces * k1;
+  const unsigned __int128 expect = (num + total - 1) / total;
+  const unsigned __int128 want = expect * 16;
+  if (want < PROOF_HIT_CAP_MIN) return (uint32_t)PROOF_HIT_CAP_MIN;
+  if (want > PROOF_HIT_CAP_MAX) return (uint32_t)PROOF_HIT_CAP_MAX;
+  return (uint32_t)want;
+}
+
+/* Queue, on `stream`, the scan of the batch at relative position pos that
+ * lies at d_labels: the set's count zeroed in front of it. */
+static int proof_launch(PostInitSession *s, hipStream_t stream, OutputSet &o,
+                        uint64_t pos, uint64_t count,
+                        const uint8_t *d_labels) {
+  ScanKernelArgs a = s->proof_scan;
+  a.labels = (const uint4 *)d_labels;
+  a.count = count;
+  a.index_base = s->range_start + pos; /* global: the parts merge as they are */
+  a.hits = o.d_hits.get();
+  a.hit_count = o.d_hit_count.get();
+  a.hit_cap = s->proof_hit_cap;
+  HIP_TRY(hipMemsetAsync(o.d_hit_count.get(), 0, sizeof(unsigned int), stream));
+  if (o.ev_scan[0].get()) HIP_TRY(hipEventRecord(o.ev_scan[0].get(), stream));
+  HIP_TRY(poste_launch_scan_resident(&a, s->proof_variant, s->proof_blocks,
+                                     stream));
+  if (o.ev_scan[1].get()) HIP_TRY(hipEventRecord(o.ev_scan[1].get(), stream));
+  return POST_OK;
+}
+
+/* the count and the first records, with the batch's other small copies */
+static int proof_queue_fetch(PostInitSession *s, hipStream_t stream,
+                             OutputSet &o) {
+  HIP_TRY(hipMemcpyAsync(o.h_hit_count.get(), o.d_hit_count.get(),
+                         sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(
+      o.h_hits.get(), o.d_hits.get(),
+      sizeof(PostScanHit) * std::min(PROOF_HIT_WINDOW, s->proof_hit_cap),
+      hipMemcpyDeviceToHost, stream));
+  return POST_OK;
+}
+
+/* The batch has arrived: its hits, sorted by (index, nonce).  More than the
+ * window is fetched here, the one case in which the host goes to the device
+ * a second time for a batch.  A count above the capacity fails the step
+ * before anything of the batch is persisted. */
+static int proof_collect(PostInitSession *s, OutputSet &o, uint64_t pos,
+                         uint64_t count, std::vector<PostScanHit> &hits) {
+  const unsigned int n = *o.h_hit_count.get();
+  float ms = 0;
+  if (o.ev_scan[0].get() &&
+      hipEventElapsedTime(&ms, o.ev_scan[0].get(), o.ev_scan[1].get()) ==
+          hipSuccess) {
+    s->proof_ms += ms;
+    s->proof_ms_max = std::max<double>(s->proof_ms_max, ms);
+    s->proof_timed++;
+  }
+  if (n > s->proof_hit_cap) {
+    set_error("scan hit buffer overflow in the init batch [" +
+              std::to_string(s->range_start + pos) + ", " +
+              std::to_string(s->range_start + pos + count) + "): " +
+              std::to_string(n) + " hits, room for " +
+              std::to_string(s->proof_hit_cap) +
+              " (pathological K1/num_labels configuration); nothing of the "
+              "batch was appended and labels written stays at " +
+              std::to_string(s->written.load()));
+    return POST_ERR;
+  }
+  hits.resize(n);
+  const unsigned int head = std::min(n, PROOF_HIT_WINDOW);
+  if (head) std::memcpy(hits.data(), o.h_hits.get(), sizeof(PostScanHit) * head);
+  if (n > head) {
+    HIP_TRY(hipMemcpy(hits.data() + head, o.d_hits.get() + head,
+                      sizeof(PostScanHit) * (n - head),
+                      hipMemcpyDeviceToHost));
+    s->proof_refetch++;
+  }
+  std::sort(hits.begin(), hits.end(),
+            [](const PostScanHit &a, const PostScanHit &b) {
+              return a.index != b.index ? a.index < b.index
+                                        : a.nonce < b.nonce;
+            });
+  return POST_OK;
+}
+
+/* The batch's labels are in the files: append its hits and one marker.  The
+ * caller advances `written` only after this. */
+static int proof_commit(PostInitSession *s, uint64_t pos, uint64_t count,
+                        const std::vector<PostScanHit> &hits) {
+  std::vector<uint8_t> rec((hits.size() + 1) * initproof::RECORD_BYTES);
+  for (size_t i = 0; i < hits.size(); i++)
+    initproof::pack_record(hits[i].index, hits[i].nonce, 0,
+                           rec.data() + i * initproof::RECORD_BYTES);
+  initproof::pack_record(s->range_start + pos + count, initproof::MARK_NONCE,
+                         initproof::MARK_TAG,
+                         rec.data() + hits.size() * initproof::RECORD_BYTES);
+  s->proof_pos = UINT64_MAX; /* a failure below leaves the part to a resync */
+  if (!initproof::write_at(s->proof_fd, rec.data(), rec.size(),
+                           s->proof_bytes)) {
+    set_error("short write to " +
+              initproof::part_path(s->data_dir, s->range_start));
+    return POST_ERR_IO;
+  }
+  s->proof_bytes += rec.size();
+  s->proof_pos = pos + count;
+  s->proof_hits += hits.size();
+  if (s->range_start + pos + count == s->range_end) {
+    (void)::close(s->proof_fd);
+    s->proof_fd = -1;
+    if (s->proof_timed)
+      std::fprintf(stderr,
+                   "init proof: %llu batches of up to %llu labels, scan (%s) "
+                   "%.3f ms per batch (max %.3f ms, %.1f ms in all), %llu "
+                   "hits, %llu batches fetched past the window\n",
+                   (unsigned long long)s->proof_timed,
+                   (unsigned long long)s->batch,
+                   s->proof_variant == POSTE_SCAN_RESIDENT_TT4 ? "tt4"
+                                                               : "bankrep",
+                   s->proof_ms / s->proof_timed, s->proof_ms_max, s->proof_ms,
+                   (unsigned long long)s->proof_hits,
+                   (unsigned long long)s->proof_refetch);
+  }
+  return POST_OK;
+}
+
+/* Part and `written` brought to one point, as a new session would: the
+ * lower of `written` and the part's last well-formed marker, the part cut
+ * there.  Nothing to do while they agree. */
+static int proof_resync(PostInitSession *s) {
+  const uint64_t w = s->written.load();
+  if (s->proof_pos == w || s->proof_fd < 0) return POST_OK;
+  uint64_t point = s->range_start + w;
+  std::string err;
+  const int rc = initproof::sync_part(s->proof_fd, s->proof_hdr, &point,
+                                      &s->proof_bytes, err);
+  if (rc != POST_OK) {
+    set_error(err + ": " + initproof::part_path(s->data_dir, s->range_start));
+    return rc;
+  }
+  s->proof_pos = point - s->range_start;
+  s->written.store(s->proof_pos);
+  return POST_OK;
+}
+
+int post_init_enable_proof(PostInitSession *s, const PostProveConfig *cfg) {
+  if (!s || !cfg || s->data_dir.empty()) {
+    set_error("initial proof during init needs a session with a data dir and "
+              "a proving config");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (s->stepped) {
+    set_error("post_init_enable_proof must be called before the first step");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (cfg->nonces == 0 || cfg->nonces % POSTE_NONCE_GROUP != 0) {
+    set_error("nonces must be a positive multiple of 16");
+    return POST_ERR_INVALID_ARGS;
+  }
+  if (cfg->pow_mode != POST_POW_MODE_BLAKE3) {
+    set_error("initial proof during init: RandomX k2pow is not supported by "
+              "this engine (use POST_POW_MODE_BLAKE3)");
+    return POST_ERR_UNSUPPORTED;
+  }
+  const uint64_t total = (uint64_t)s->cfg.num_units * s->cfg.labels_per_unit;
+  const uint64_t range = s->range_end - s->range_start;
+  initproof::Header h;
+  h.nonces = cfg->nonces;
+  h.k1 = cfg->k1;
+  h.k2 = cfg->k2;
+  std::memcpy(h.challenge, cfg->challenge, 32);
+  std::memcpy(h.pow_difficulty, cfg->pow_difficulty, 32);
+  h.index_start = s->range_start;
+  h.index_end = s->range_end;
+  h.total_labels = total;
+  uint8_t hdr[initproof::HEADER_BYTES];
+  initproof::pack_header(h, hdr);
+  if (s->proof_on) {
+    /* a second call: fine with the config in force, refused with another */
+    uint8_t have[initproof::HEADER_BYTES];
+    initproof::pack_header(s->proof_hdr, have);
+    if (std::memcmp(have, hdr, sizeof hdr) == 0) return POST_OK;
+    set_error("the initial proof is already enabled with another proving "
+              "config");
+    return POST_ERR_INVALID_ARGS;
+  }
+  const std::string part = initproof::part_path(s->data_dir, s->range_start);
+  struct stat st;
+  const bool have_part = ::stat(part.c_str(), &st) == 0;
+  if (!have_part && s->written.load() > 0) {
+    set_error("dir was started without the proof scan; finish init and run "
+              "prove");
+    return POST_ERR_UNSUPPORTED;
+  }
+  /* POST_INIT_PROOF_SCAN picks the variant, once: bankrep (default) or tt4.
+   * Judged before the dir is touched. */
+  int variant = POSTE_SCAN_RESIDENT_BANKREP;
+  if (const char *mode = getenv("POST_INIT_PROOF_SCAN")) {
+    if (std::strcmp(mode, "tt4") == 0) {
+      variant = POSTE_SCAN_RESIDENT_TT4;
+    } else if (*mode && std::strcmp(mode, "bankrep") != 0) {
+      set_error("POST_INIT_PROOF_SCAN must be bankrep or tt4");
+      return POST_ERR_INVALID_ARGS;
+    }
+  }
+  s->proof_hdr = h;
+  if (s->proof_fd >= 0) (void)::close(s->proof_fd); /* an earlier failed call */
+  s->proof_fd = ::open(part.c_str(), O_RDWR | O_CREAT, 0644);
+  if (s->proof_fd < 0) {
+    set_error("cannot open " + part);
+    return POST_ERR_IO;
+  }
+  /* a call that fails leaves the dir as it found it: a part it created
+   * would otherwise make a later session take a dir that went on without the
+   * scan for one that had it */
+  auto drop = [s, have_part, &part](int rc) {
+    (void)::close(s->proof_fd);
+    s->proof_fd = -1;
+    if (!have_part) (void)::unlink(part.c_str());
+    return rc;
+  };
+  if (have_part) {
+    uint8_t got[initproof::HEADER_BYTES];
+    if ((uint64_t)st.st_size < initproof::HEADER_BYTES ||
+        ::pread(s->proof_fd, got, sizeof got, 0) != (ssize_t)sizeof got ||
+        std::memcmp(got, hdr, sizeof got) != 0) {
+      set_error(part + " has a header that disagrees with the session or "
+                       "with the proving config");
+      return drop(POST_ERR_IO);
+    }
+  } else if (!initproof::write_at(s->proof_fd, hdr, sizeof hdr, 0)) {
+    set_error("cannot write " + part);
+    return drop(POST_ERR_IO);
+  }
+  /* the resume point: labels on disk (and the seal's, which `written`
+   * already holds) against the part's last marker */
+  s->proof_pos = UINT64_MAX;
+  int rc = proof_resync(s);
+  if (rc != POST_OK) return drop(rc);
+  if (s->seal_on) {
+    /* the seal continues from a page boundary only */
+    rc = seal_resync(s);
+    if (rc == POST_OK) rc = proof_resync(s);
+    if (rc != POST_OK) return drop(rc);
+  }
+  if (s->written.load() == range) {
+    /* complete; nothing left to scan */
+    (void)::close(s->proof_fd);
+    s->proof_fd = -1;
+    return POST_OK;
+  }
+
+  rc = require_gpu(s->cfg.provider_id);
+  if (rc != POST_OK) return drop(rc);
+  DeviceTables tbl;
+  rc = get_aes_tables((int)s->cfg.provider_id, tbl);
+  if (rc != POST_OK) return drop(rc);
+  /* POST_SCAN_MAX_BLOCKS lowers the grid cap as on the prove path, read
+   * here and not per launch */
+  s->proof_variant = variant;
+  {
+    const hipError_t e = poste_scan_resident_prepare(s->proof_variant);
+    if (e != hipSuccess) return drop(hip_fail("poste_scan_resident_prepare", e));
+  }
+  s->proof_blocks =
+      s->proof_variant == POSTE_SCAN_RESIDENT_TT4 ? 2048u : 8192u;
+  if (const char *e = getenv("POST_SCAN_MAX_BLOCKS")) {
+    const long v = strtol(e, nullptr, 10);
+    if (v >= 1 && v < (long)s->proof_blocks) s->proof_blocks = (uint32_t)v;
+  }
+  s->proof_hit_cap =
+      proof_hit_capacity(s->batch, cfg->nonces, cfg->k1, total);
+
+  const uint32_t n_ciphers = cfg->nonces / POSTE_NONCES_PER_AES;
+  std::vector<uint32_t> rk((size_t)n_ciphers * 44);
+  {
+    std::vector<uint64_t> group_pow(cfg->nonces / POSTE_NONCE_GROUP);
+    for (uint32_t g = 0; g < group_pow.size(); g++)
+      group_pow[g] = poste::k2pow_search_blake3(
+          cfg->challenge, g, cfg->pow_difficulty, cfg->pow_threads);
+    for (uint32_t c = 0; c < n_ciphers; c++) {
+      uint8_t key[16];
+      const uint32_t grp = (c * POSTE_NONCES_PER_AES) / POSTE_NONCE_GROUP;
+      poste::prove_cipher_key(cfg->challenge, c, group_pow[grp], key);
+      poste::aes128_expand(key, rk.data() + (size_t)c * 44);
+    }
+  }
+  auto hip_drop = [&drop](const char *what, hipError_t e) {
+    return drop(hip_fail(what, e));
+  };
+  hipError_t e = s->d_proof_rk.alloc(rk.size() * 4);
+  if (e == hipSuccess)
+    e = hipMemcpy(s->d_proof_rk.get(), rk.data(), rk.size() * 4,
+                  hipMemcpyHostToDevice);
+  const bool debug = getenv("POST_INIT_PROOF_DEBUG") != nullptr;
+  for (int i = 0; i < (s->split_streams ? 2 : 1) && e == hipSuccess; i++) {
+    OutputSet &o = s->set[i];
+    e = o.d_hits.alloc(sizeof(PostScanHit) * s->proof_hit_cap);
+    if (e == hipSuccess) e = o.d_hit_count.alloc(sizeof(unsigned int));
+    if (e == hipSuccess)
+      e = o.h_hits.alloc(sizeof(PostScanHit) * PROOF_HIT_WINDOW);
+    if (e == hipSuccess) e = o.h_hit_count.alloc(sizeof(unsigned int));
+    for (Event &ev : o.ev_scan)
+      if (debug && e == hipSuccess) e = ev.create();
+  }
+  if (e != hipSuccess) return hip_drop("initial proof buffers", e);
+  std::memset(&s->proof_scan, 0, sizeof(s->proof_scan));
+  s->proof_scan.te = tbl.d_te;
+  s->proof_scan.sbox = tbl.d_sbox;
+  s->proof_scan.rk = s->d_proof_rk.get();
+  s->proof_scan.n_ciphers = n_ciphers;
+  s->proof_scan.difficulty = poste::proving_difficulty(cfg->k1, total);
+  s->proof_on = true;
+  return POST_OK;
+}
+
 /* ------------------- host half of an init batch -------------------
  *
  * Shared by the monolithic step, the split step and the nonce search past
@@ -1065,7 +1423,7 @@ struct SelfCheck {
  * are merged: check it, persist it, count it. */
 static int finish_batch(PostInitSession *s, OutputSet &o, const SelfCheck &sc,
                         uint64_t pos, uint64_t count, bool nonce_improved,
-                        uint64_t *done) {
+                        const std::vector<PostScanHit> &hits, uint64_t *done) {
   int rc;
   /* persist an improved running minimum immediately: metadata is the
    * only carrier of the shard-local minimum across kill+resume (the
@@ -1094,6 +1452,11 @@ static int finish_batch(PostInitSession *s, OutputSet &o, const SelfCheck &sc,
   /* digests only behind their labels (a seal needs a data dir) */
   if (s->seal_on) {
     rc = seal_commit(s, o, pos, count);
+    if (rc != POST_OK) return rc;
+  }
+  /* hits only behind their labels, the marker behind the hits */
+  if (s->proof_on) {
+    rc = proof_commit(s, pos, count, hits);
     if (rc != POST_OK) return rc;
   }
   s->written.store(pos + count);
@@ -1239,6 +1602,12 @@ static int init_step_split(PostInitSession *s, SelfCheck &sc,
       const int rc = seal_launch(s, copy_stream, o, b.pos, b.count, out);
       if (rc != POST_OK) return rc;
     }
+    /* the proving scan of the batch, at the same point: it reads what the
+     * tails wrote and nothing else of the batch */
+    if (s->proof_on) {
+      const int rc = proof_launch(s, copy_stream, o, b.pos, b.count, out);
+      if (rc != POST_OK) return rc;
+    }
     HIP_TRY(hipMemcpyAsync(o.h_batch.get(), out, b.count * POST_LABEL_SIZE,
                            hipMemcpyDeviceToHost, copy_stream));
     HIP_TRY(hipMemcpyAsync(o.h_cand_count.get(), o.d_cand_count.get(),
@@ -1250,6 +1619,10 @@ static int init_step_split(PostInitSession *s, SelfCheck &sc,
     HIP_TRY(hipMemcpyAsync(o.h_cand.get(), o.d_cand.get(),
                            sizeof(PostVrfCandidate) * b.max_cand,
                            hipMemcpyDeviceToHost, copy_stream));
+    if (s->proof_on) {
+      const int rc = proof_queue_fetch(s, copy_stream, o);
+      if (rc != POST_OK) return rc;
+    }
     HIP_TRY(hipEventRecord(o.ev_done.get(), copy_stream));
     last_set = b.set;
     b.live = true;
@@ -1262,10 +1635,15 @@ static int init_step_split(PostInitSession *s, SelfCheck &sc,
     OutputSet &o = s->set[b.set];
     sc.begin(s, b.pos, b.count);
     HIP_TRY(hipEventSynchronize(o.ev_done.get()));
+    std::vector<PostScanHit> hits;
+    if (s->proof_on) {
+      const int rc = proof_collect(s, o, b.pos, b.count, hits);
+      if (rc != POST_OK) return rc;
+    }
     const unsigned int take = std::min(*o.h_cand_count.get(), b.max_cand);
     const bool improved =
         merge_candidates(s, o.h_cand.get(), take, cur_difficulty);
-    return finish_batch(s, o, sc, b.pos, b.count, improved, done);
+    return finish_batch(s, o, sc, b.pos, b.count, improved, hits, done);
   };
 
   auto run = [&]() -> int {
@@ -1324,8 +1702,18 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
   int rc = require_gpu(s->cfg.provider_id);
   if (rc != POST_OK) return rc;
   s->stepped = true;
+  /* after a failed step: the part back to its marker, the seal back to its
+   * page boundary, and the part once more when that moved `written` */
+  if (s->proof_on) {
+    rc = proof_resync(s);
+    if (rc != POST_OK) return rc;
+  }
   if (s->seal_on) {
     rc = seal_resync(s);
+    if (rc != POST_OK) return rc;
+  }
+  if (s->proof_on) {
+    rc = proof_resync(s);
     if (rc != POST_OK) return rc;
   }
   SelfCheck sc;
@@ -1369,13 +1757,26 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
       rc = seal_launch(s, stream, o, pos, count, args.out);
       if (rc != POST_OK) return rc;
     }
+    if (s->proof_on) {
+      rc = proof_launch(s, stream, o, pos, count, args.out);
+      if (rc != POST_OK) return rc;
+    }
     HIP_TRY(hipMemcpyAsync(o.h_batch.get(), args.out, count * POST_LABEL_SIZE,
                            hipMemcpyDeviceToHost, stream));
     unsigned int n_cand = 0;
     HIP_TRY(hipMemcpyAsync(&n_cand, o.d_cand_count.get(), sizeof(n_cand),
                            hipMemcpyDeviceToHost, stream));
+    if (s->proof_on) {
+      rc = proof_queue_fetch(s, stream, o);
+      if (rc != POST_OK) return rc;
+    }
     sc.begin(s, pos, count);
     HIP_TRY(hipStreamSynchronize(stream));
+    std::vector<PostScanHit> hits;
+    if (s->proof_on) {
+      rc = proof_collect(s, o, pos, count, hits);
+      if (rc != POST_OK) return rc;
+    }
     bool nonce_improved = false;
     if (n_cand > 0) {
       unsigned int take = std::min(n_cand, s->cand_cap);
@@ -1384,7 +1785,7 @@ int post_init_step(PostInitSession *s, uint64_t max_labels, uint64_t *done) {
                         hipMemcpyDeviceToHost));
       nonce_improved = merge_candidates(s, cands.data(), take, cur_difficulty);
     }
-    rc = finish_batch(s, o, sc, pos, count, nonce_improved, done);
+    rc = finish_batch(s, o, sc, pos, count, nonce_improved, hits, done);
     if (rc != POST_OK) return rc;
     float ms = 0;
     (void)hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get());
@@ -1740,41 +2141,12 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
     if (rc != POST_OK) return rc;
   }
 
-  /* winner: nonce whose k2-th smallest passing index is smallest
-   * (streaming-order first across the ascending scan); tie -> lowest nonce */
-  std::vector<std::vector<uint64_t>> per_nonce(cfg->nonces);
-  for (const auto &h : all_hits) per_nonce[h.nonce].push_back(h.index);
-  int64_t best_nonce = -1;
-  uint64_t best_kth = UINT64_MAX;
-  for (uint32_t nn = 0; nn < cfg->nonces; nn++) {
-    auto &v = per_nonce[nn];
-    if (v.size() < cfg->k2) continue;
-    std::sort(v.begin(), v.end());
-    uint64_t kth = v[cfg->k2 - 1];
-    if (kth < best_kth) {
-      best_kth = kth;
-      best_nonce = nn;
-    }
-  }
-  if (best_nonce < 0) {
-    set_error("no nonce reached k2 passing indices");
-    return POST_ERR_NO_NONCE;
-  }
-  out->nonce = (uint32_t)best_nonce;
-  out->pow = group_pow[best_nonce / POSTE_NONCE_GROUP];
-  out->num_indices = (uint16_t)cfg->k2;
-  uint32_t bpi = poste::bits_per_index(num_labels);
-  out->indices_len = poste::pack_indices(per_nonce[best_nonce].data(),
-                                         cfg->k2, bpi, out->indices,
-                                         POST_MAX_INDICES_BYTES);
-  if (!out->indices_len) {
-    set_error("indices exceed the 800-byte wire cap");
-    return POST_ERR;
-  }
-  if (winner)
-    winner->assign(per_nonce[best_nonce].begin(),
-                   per_nonce[best_nonce].begin() + cfg->k2);
-  return POST_OK;
+  /* the winner rule, shared with the assembly of an init's hit parts */
+  std::string err;
+  rc = initproof::choose_winner(all_hits, cfg->nonces, cfg->k2, num_labels,
+                                group_pow, out, winner, err);
+  if (rc != POST_OK) set_error(err);
+  return rc;
 }
 
 int post_prove_buffer(const uint8_t *labels, uint64_t num_labels,
@@ -3336,6 +3708,22 @@ int post_seal_assemble(const char *data_dir, uint64_t *pages) {
     return POST_ERR_INVALID_ARGS;
   }
   return seal_assemble(data_dir, pages, false);
+}
+
+/* the hit parts of DESIGN 3.8 merged into the initial proof; reads only */
+int post_init_proof_assemble(const char *data_dir, PostProof *out,
+                             PostInitProofReport *r) {
+  if (!data_dir || !out) {
+    set_error("null args");
+    return POST_ERR_INVALID_ARGS;
+  }
+  DirMetadata md;
+  int rc = read_dir_metadata(data_dir, md);
+  if (rc != POST_OK) return rc;
+  std::string err;
+  rc = initproof::assemble_dir(data_dir, md.total, out, r, err);
+  if (rc != POST_OK) set_error(err);
+  return rc;
 }
 
 int post_seal_digest_stream(const uint8_t *labels, uint64_t count,

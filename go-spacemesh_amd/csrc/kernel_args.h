@@ -147,6 +147,20 @@ hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
                                            hipStream_t stream);
 hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
                                     uint32_t blocks, hipStream_t stream);
+/* The scan over a resident batch on the caller's stream (init with the
+ * initial proof): the kernels of poste_launch_scan_kernel, no
+ * environment read per launch.  prepare is called once per process and
+ * variant, outside any stream (tt4: the 128 KiB dynamic-LDS opt-in; an error
+ * means the variant cannot run here).  The grid is min(ceil(count /
+ * threads), max_blocks) with threads = poste_scan_resident_threads(variant);
+ * hipErrorInvalidValue for an unset pointer, an empty batch or no block. */
+#define POSTE_SCAN_RESIDENT_TT4 0
+#define POSTE_SCAN_RESIDENT_BANKREP 1
+hipError_t poste_scan_resident_prepare(int variant);
+uint32_t poste_scan_resident_threads(int variant);
+hipError_t poste_launch_scan_resident(const ScanKernelArgs *args, int variant,
+                                      uint32_t max_blocks,
+                                      hipStream_t stream);
 /* one lane per page; hipErrorInvalidValue for an empty or unset buffer */
 hipError_t poste_launch_seal_kernel(const SealKernelArgs *args,
                                     hipStream_t stream);

@@ -1634,4 +1634,43 @@ hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
   }
   return hipGetLastError();
 }
+
+/* The proving scan over a batch that already lies in device memory (an init
+ * batch behind its tail kernels), on the caller's stream.  The
+ * kernels are those of poste_launch_scan_kernel, unchanged; what differs is
+ * that nothing is read from the environment per launch: the session picks
+ * the variant once, prepares it once (the 128 KiB dynamic-LDS opt-in of tt4
+ * is a function attribute, set outside any stream), and fixes the grid cap. */
+hipError_t poste_scan_resident_prepare(int variant) {
+  if (variant == POSTE_SCAN_RESIDENT_BANKREP) return hipSuccess;
+  if (variant != POSTE_SCAN_RESIDENT_TT4) return hipErrorInvalidValue;
+  return hipFuncSetAttribute((const void *)post_scan_tt4_kernel,
+                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                             32768 * 4);
+}
+
+uint32_t poste_scan_resident_threads(int variant) {
+  return variant == POSTE_SCAN_RESIDENT_TT4 ? 1024 : POSTE_THREADS;
+}
+
+hipError_t poste_launch_scan_resident(const ScanKernelArgs *args, int variant,
+                                      uint32_t max_blocks,
+                                      hipStream_t stream) {
+  if (!args->labels || !args->hits || !args->hit_count || args->count == 0 ||
+      max_blocks == 0)
+    return hipErrorInvalidValue;
+  const uint32_t threads = poste_scan_resident_threads(variant);
+  const uint64_t need = (args->count + threads - 1) / threads;
+  const uint32_t blocks = need < max_blocks ? (uint32_t)need : max_blocks;
+  if (variant == POSTE_SCAN_RESIDENT_TT4)
+    hipLaunchKernelGGL(post_scan_tt4_kernel, dim3(blocks), dim3(1024),
+                       32768 * 4, stream, *args);
+  else if (variant == POSTE_SCAN_RESIDENT_BANKREP)
+    hipLaunchKernelGGL((post_scan_bankrep_kernel<POSTE_THREADS, false>),
+                       dim3(blocks), dim3(POSTE_THREADS), 8192 * 4, stream,
+                       *args);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
 }

@@ -464,6 +464,92 @@ int post_seal_digest_stream(const uint8_t *labels, uint64_t count,
                             uint32_t provider_id, uint8_t *digests,
                             uint64_t cap_pages, uint64_t *n_pages);
 
+/* ---------- initial proof during init ---------- */
+/* A node proves over the zero challenge as soon as init ends
+ * (activation/activation.go:350-402, BuildInitialPost); done with post_prove
+ * that is a second read of every byte just written.  A session that opts in
+ * runs the proving scan over every batch while it lies in device memory
+ * behind the label kernels, so a finished init has the hits
+ * of its range on disk and the proof is a host-only merge.  Off by default;
+ * a session that does not opt in queues exactly what it queued before.
+ *
+ * While a session runs, the hits of its range are appended to
+ * postdata_hits.part-<index_start>, little-endian: a 128-byte header {magic
+ * "PSTHITSP", u32 record_bytes = 16, u32 nonces, u32 k1, u32 k2,
+ * challenge[32], pow_difficulty[32], u64 index_start, u64 index_end,
+ * u64 total_labels, zeros}, then 16-byte records {u64 index, u32 nonce,
+ * u32 tag}.  A hit has tag 0; a marker has nonce 0xFFFFFFFF, tag 0x4B52414D
+ * and index = the global index up to which the part is complete.  After the
+ * labels of a batch are in the files its hits are appended, sorted by
+ * (index, nonce), then one marker; only then does
+ * post_init_num_labels_written advance.  The file is ascending, hits are on
+ * disk only behind their labels, and every hit is kept (nonces * k1 in
+ * expectation over the whole space).
+ *
+ * A new session over the same range drops what follows the last well-formed
+ * marker, resumes at min(labels on disk, last marker, the seal's resume point
+ * when the seal is on as well), cuts the part at the first record at or past
+ * that point and writes a marker there.  A step that follows a failed step
+ * does the same.
+ *
+ * The difficulty is that of the whole space (NumUnits * LabelsPerUnit), the
+ * indices are global, and the k2pow is the smallest one, so shards need no
+ * coordination.  The device hit buffer of a batch holds
+ * clamp(16 * ceil(batch * nonces * k1 / total_labels), 4096, 65536) records
+ * (batch = labels per launch); a batch with more hits fails its step with
+ * POST_ERR: nothing of it is appended and post_init_num_labels_written does
+ * not advance.
+ *
+ * The host gets the count of a batch and its first 1024 records with the
+ * batch's other results; a batch with more hits is fetched a second time,
+ * which waits for everything queued on the device.
+ *
+ * Environment, read once by post_init_enable_proof and never per launch:
+ * POST_INIT_PROOF_SCAN = bankrep (default) or tt4 picks the scan kernel, both
+ * leave identical parts (anything else: POST_ERR_INVALID_ARGS, judged before
+ * the dir is touched); POST_SCAN_MAX_BLOCKS lowers the scan's grid cap as it
+ * does for post_prove; POST_INIT_PROOF_DEBUG times the scan of every batch
+ * with device events and prints the figures on stderr when the range is
+ * complete.
+ *
+ * Not covered: sessions without a data dir, RandomX, a challenge that is not
+ * known when init starts, a dir started without the scan.
+ *
+ * Call after post_init_new (and post_init_enable_seal) and before the first
+ * post_init_step; cfg->provider_id is ignored, the session's is used.
+ * Validated in this order, all of it before a GPU is required:
+ * POST_ERR_INVALID_ARGS for a NULL session, a NULL cfg or a session without a
+ * data dir; POST_ERR_INVALID_ARGS after the first step;
+ * POST_ERR_INVALID_ARGS for nonces zero or no multiple of 16;
+ * POST_ERR_UNSUPPORTED for a pow_mode other than blake3;
+ * POST_ERR_UNSUPPORTED for a range that has labels on disk and no part file;
+ * POST_ERR_IO for a part file whose header disagrees with the session or
+ * with cfg.  A call that fails leaves no part file behind that it created.
+ * A second call with the config in force is POST_OK, with another one
+ * POST_ERR_INVALID_ARGS. */
+int post_init_enable_proof(PostInitSession *s, const PostProveConfig *cfg);
+
+typedef struct {
+  uint64_t total_labels;   /* NumUnits * LabelsPerUnit */
+  uint64_t labels_covered; /* by the parts found */
+  uint64_t hits;           /* records in the merged list */
+  uint32_t parts;
+  uint32_t reserved;
+} PostInitProofReport;
+
+/* Host only, no GPU, reads only: merge the part files of data_dir and choose
+ * the winner by the rule of post_prove; the proof is the one post_prove
+ * returns on the finished dir.  The parts must agree in everything but
+ * their range, tile [0, NumUnits * LabelsPerUnit) of postdata_metadata.json
+ * with no gap or overlap, and each must be complete (its last marker at its
+ * index_end): otherwise POST_ERR_IO, the message naming the first missing
+ * index range.  POST_ERR_NO_NONCE when no nonce reaches K2 (post_prove fails
+ * the same way).  It writes nothing and removes nothing, so it may be called
+ * at any time and any number of times; r may be NULL and is filled whenever
+ * the tiling was complete. */
+int post_init_proof_assemble(const char *data_dir, PostProof *out,
+                             PostInitProofReport *r);
+
 /* ---------- self-healing prove ---------- */
 /* What the seal pass finds bad is put right in the same call (DESIGN.md
  * 3.6): the bad pages are recomputed on the GPU from the identity in

@@ -11,7 +11,9 @@ verification, provider listing and benchmarking
     python postcli.py benchmark [--scrypt-n 8192]
     python postcli.py init --datadir DIR --node-id HEX32 --atx-id HEX32 \
         --num-units U [--labels-per-unit L] [--scrypt-n N] \
-        [--max-file-size B] [--shard R/W] [--seal]
+        [--max-file-size B] [--shard R/W] [--seal] \
+        [--initial-proof [--k1 K] [--k2 K] [--nonces 288]]
+    python postcli.py initial-proof --datadir DIR
     python postcli.py prove --datadir DIR --challenge HEX32 [--nonces 288] \
         [--check-seal [--max-report N] \
          [--heal [--write-back] [--max-heal-pages N]]]
@@ -45,6 +47,14 @@ postdata_seal.bin; seal --assemble does that assembly by hand (no GPU) and
 exits with status 2, naming the missing pages, while a shard is unfinished.
 A shard that is not made of whole 1024-label pages is refused (status 2).
 
+init --initial-proof runs the proving scan for the zero challenge over every
+batch while it lies in device memory and appends the hits to
+postdata_hits.part-<index_start>; when its range completes and the parts of
+all shards are there it writes initial_proof.json into the dir, in the format
+prove prints, and otherwise says which range is outstanding.  initial-proof
+does that merge alone (no GPU; exit status 1 while a range is outstanding or
+when no nonce reaches K2).  Either output is accepted by verify as it is.
+
 prove --check-seal --heal puts the bad pages right in the same call (DESIGN
 §3.6): they are recomputed on the GPU, their hits replaced, and the proof is
 the one the undamaged dir gives; --write-back also writes the pages the seal
@@ -57,6 +67,7 @@ status 0 when a following check-seal would be clean.
 import argparse
 import base64
 import json
+import os
 import sys
 import threading
 import time
@@ -100,6 +111,33 @@ def _mk_cfg(args):
     return cfg
 
 
+def _proof_json(proof, challenge, seconds):
+    """A proof as prove prints it and verify reads it."""
+    return {"nonce": proof.nonce,
+            "indices": base64.b64encode(proof.indices).decode(),
+            "pow": proof.pow,
+            "challenge": challenge.hex(),
+            "seconds": round(seconds, 2),
+            "scale_encoded_postv1": wire.PostV1(
+                proof.nonce, proof.indices, proof.pow).encode().hex()}
+
+
+ZERO_CHALLENGE = bytes(32)          # shared.ZeroChallenge
+
+
+def cmd_initial_proof(args):
+    t0 = time.time()
+    try:
+        proof, rep = gsm_amd.init_proof_assemble(args.datadir)
+    except gsm_amd.EngineError as e:
+        print(f"initial-proof failed: {e}", file=sys.stderr)
+        return 1
+    print(f"initial proof from {rep.parts} part(s), {rep.hits} hits over "
+          f"{rep.labels_covered} labels", file=sys.stderr)
+    print(json.dumps(_proof_json(proof, ZERO_CHALLENGE, time.time() - t0)))
+    return 0
+
+
 def cmd_init(args):
     node = bytes.fromhex(args.node_id)
     atx = bytes.fromhex(args.atx_id)
@@ -119,14 +157,29 @@ def cmd_init(args):
         scrypt_n=args.scrypt_n, index_start=start, index_end=end)
     if args.seal:
         opts.seal = True
+    if not args.initial_proof and (args.k1 is not None or args.k2 is not None
+                                   or args.nonces is not None):
+        raise SystemExit("--k1, --k2 and --nonces need --initial-proof")
+    if args.initial_proof:
+        ip = gsm_amd.InitialProofOpts.of(cfg, challenge=ZERO_CHALLENGE)
+        if args.k1 is not None:
+            ip.k1 = args.k1
+        if args.k2 is not None:
+            ip.k2 = args.k2
+        if args.nonces is not None:
+            ip.nonces = args.nonces
+        opts.initial_proof = ip
     mgr = gsm_amd.PostSetupManager(node, atx, cfg, opts)
-    if args.seal:
+    if args.seal or args.initial_proof:
         # what a sealed session refuses (an unaligned shard, a dir started
         # without a seal) is the operator's to put right, like a bad sidecar
         try:
             mgr.prepare_initializer()
         except gsm_amd.EngineError as e:
-            print(f"init --seal failed: {e}", file=sys.stderr)
+            flags = " ".join(f for f, on in (("--seal", args.seal),
+                                             ("--initial-proof",
+                                              args.initial_proof)) if on)
+            print(f"init {flags} failed: {e}", file=sys.stderr)
             return 2
     else:
         mgr.prepare_initializer()
@@ -159,6 +212,20 @@ def cmd_init(args):
         "vrf_nonce": nonce[0] if nonce else None,
     }))
     mgr.reset()
+    if args.initial_proof:
+        # the range is complete: merge, when every shard's part is there
+        t0 = time.time()
+        try:
+            proof, _ = gsm_amd.init_proof_assemble(args.datadir)
+        except gsm_amd.EngineError as e:
+            print(f"initial proof not written: {e}", file=sys.stderr)
+            return 0
+        path = os.path.join(args.datadir, "initial_proof.json")
+        with open(path, "w") as f:
+            json.dump(_proof_json(proof, ZERO_CHALLENGE, time.time() - t0), f)
+            f.write("\n")
+        print(f"initial proof written to {path}", file=sys.stderr)
+    return 0
 
 
 def cmd_prove(args):
@@ -227,14 +294,8 @@ def cmd_prove(args):
         proof = gsm_amd.api.prove_dir(args.datadir,
                                       bytes.fromhex(args.challenge), cfg,
                                       gsm_amd.ProveOpts(nonces=args.nonces))
-    out = {"nonce": proof.nonce,
-           "indices": base64.b64encode(proof.indices).decode(),
-           "pow": proof.pow,
-           "challenge": args.challenge,
-           "seconds": round(time.time() - t0, 2),
-           "scale_encoded_postv1": wire.PostV1(
-               proof.nonce, proof.indices, proof.pow).encode().hex()}
-    print(json.dumps(out))
+    print(json.dumps(_proof_json(proof, bytes.fromhex(args.challenge),
+                                 time.time() - t0)))
 
 
 def cmd_seal(args):
@@ -422,7 +483,15 @@ def build_parser():
     i.add_argument("--pow-difficulty", default=None)
     i.add_argument("--seal", action="store_true",
                    help="write postdata_seal.bin from the device during init")
+    i.add_argument("--initial-proof", action="store_true",
+                   help="scan for the zero-challenge proof during init")
+    i.add_argument("--k1", type=int, default=None)
+    i.add_argument("--k2", type=int, default=None)
+    i.add_argument("--nonces", type=int, default=None)
     i.set_defaults(fn=cmd_init)
+    ip = sub.add_parser("initial-proof")
+    ip.add_argument("--datadir", required=True)
+    ip.set_defaults(fn=cmd_initial_proof)
     p = sub.add_parser("prove")
     p.add_argument("--datadir", required=True)
     p.add_argument("--challenge", required=True)
