@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """bench_aux.py — auxiliary measurements: the proving scan (BASELINE
 config 4 shape), proving over a sealed dir with the seal checked in the same
-pass (against plain proving over that dir), and batched verification
-(config 5 shape) on one MI355X.
+pass (against plain proving over that dir), batched verification
+(config 5 shape) and batched VRF-nonce checks on one MI355X.
 
 Prints one JSON line per measurement.  Run on a GPU box:
     python bench_aux.py [--scan-labels LOG2] [--verify-proofs N]
-(--verify-proofs 0 leaves the verification legs out.)
+                        [--vrf-items N]
+(--verify-proofs 0 leaves the verification legs out, --vrf-items 0 the VRF
+leg.)
 
 These are recorded alongside the main bench (profiles/aux_rNN.json); the
 headline metric stays bench.py's labels/s.
@@ -195,10 +197,111 @@ def bench_verify(n_proofs: int):
     }))
 
 
+REPEATS = 20    # timed calls per batched figure: best and mean are reported
+
+
+def bench_vrf(n_items: int):
+    """VRF-nonce checks at mainnet scryptN = 8192, at the C-ABI boundary
+    (marshalled once, warmed at full size as bench_verify does): n_items in
+    one post_verify_vrf_nonce_batch call, the single call looped over 64 of
+    them, and a K3 = 1 proof batch of the same size for comparison (one
+    label per proof, plus pow, unpack and the AES predicate)."""
+    total = 1 << 20
+    ver = gsm_amd.PostVerifier(
+        gsm_amd.PostConfig(min_num_units=1, labels_per_unit=total, k1=26,
+                           k2=37, k3=1, pow_difficulty=MAINNET_POW_DIFF),
+        scrypt_n=8192)
+    meta = gsm_amd.PostProofMetadata(NODE, ATX, bytes(32), 1, total)
+    metas = [meta] * n_items
+    indices = [(i * 7919) % total for i in range(n_items)]
+    mar = ver.marshal_vrf(metas, indices)
+    ver.verify_vrf_nonce_batch_marshalled(mar)          # warm-up, full size
+    times = []
+    for _ in range(REPEATS):
+        t0 = time.perf_counter()
+        res = ver.verify_vrf_nonce_batch_marshalled(mar)
+        times.append(time.perf_counter() - t0)
+    ok = sum(1 for s in res if s == gsm_amd.api.Status.OK)
+    bad = sum(1 for s in res if s == gsm_amd.api.Status.INVALID_INDEX)
+    assert ok + bad == n_items
+
+    n_single = min(64, n_items)
+    cm = meta.to_c()
+    lib = ver.engine.lib
+    from ctypes import byref
+    t0 = time.perf_counter()
+    single = [lib.post_verify_vrf_nonce(byref(cm), indices[i], 8192, 0)
+              for i in range(n_single)]
+    dt_single = time.perf_counter() - t0
+    assert single == [int(s) for s in res[:n_single]]
+    print(json.dumps({
+        "metric": "verify_vrf_nonce_items_per_sec",
+        "value": round(n_items / min(times), 1),
+        "unit": "items/s",
+        "mean_items_per_sec": round(n_items * len(times) / sum(times), 1),
+        "seconds": [round(x, 4) for x in times],
+        "single_call_items_per_sec": round(n_single / dt_single, 1),
+        "config": {"items": n_items, "single_call_items": n_single,
+                   "scrypt_n": 8192, "num_labels": total,
+                   "passing": ok, "boundary": "C ABI, marshalled once"},
+    }))
+
+    # the K3 = 1 proof batch of the same size, same build and box
+    opts = gsm_amd.PostSetupOpts(num_units=1, scrypt_n=8192)
+    cfg = ver.cfg
+    mgr = gsm_amd.PostSetupManager(NODE, ATX, cfg, opts)
+    mgr.prepare_initializer()
+    mgr.start_session()
+    labels = mgr.copy_labels(0, total)
+    mgr.reset()
+    base = []
+    for c in range(4):
+        challenge = bytes([c]) * 32
+        base.append((challenge, gsm_amd.api.prove_buffer(
+            labels, total, NODE, ATX, challenge, cfg,
+            gsm_amd.ProveOpts(nonces=288))))
+    del labels
+    proofs = [base[i % 4][1] for i in range(n_items)]
+    pmetas = [gsm_amd.PostProofMetadata(NODE, ATX, base[i % 4][0], 1, total)
+              for i in range(n_items)]
+    vopts = gsm_amd.VerifyOpts(subset_seed=b"peer-seed")
+    pmar = ver.marshal_batch(proofs, pmetas)
+    ver.verify_batch(None, None, vopts, marshalled=pmar)
+    ptimes = []
+    for _ in range(REPEATS):
+        t0 = time.perf_counter()
+        pres = ver.verify_batch(None, None, vopts, marshalled=pmar)
+        ptimes.append(time.perf_counter() - t0)
+    assert all(s == gsm_amd.api.Status.OK for s, _ in pres)
+    # and both kinds in one call
+    ver.verify_batch(None, None, vopts, marshalled=pmar, vrf=mar)
+    mtimes = []
+    for _ in range(REPEATS):
+        t0 = time.perf_counter()
+        ver.verify_batch(None, None, vopts, marshalled=pmar, vrf=mar)
+        mtimes.append(time.perf_counter() - t0)
+    print(json.dumps({
+        "metric": "verify_k3_1_proofs_per_sec_same_size",
+        "value": round(n_items / min(ptimes), 1),
+        "unit": "proofs/s",
+        "mean_proofs_per_sec": round(n_items * len(ptimes) / sum(ptimes), 1),
+        "seconds": [round(x, 4) for x in ptimes],
+        "mixed_call_seconds": [round(x, 4) for x in mtimes],
+        "mixed_call_pairs_per_sec": round(n_items / min(mtimes), 1),
+        "mixed_call_mean_pairs_per_sec": round(
+            n_items * len(mtimes) / sum(mtimes), 1),
+        "config": {"proofs": n_items, "k3": 1, "k2": 37, "scrypt_n": 8192,
+                   "boundary": "C ABI, marshalled once",
+                   "mixed_call": "the proofs and the VRF items above in "
+                                 "one post_verify_batch_vrf"},
+    }))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scan-labels", type=int, default=23)  # 2^23 = 128 MiB
     ap.add_argument("--verify-proofs", type=int, default=1000)
+    ap.add_argument("--vrf-items", type=int, default=10000)
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs a GPU"
@@ -207,6 +310,8 @@ def main():
     del labels
     if args.verify_proofs > 0:
         bench_verify(args.verify_proofs)
+    if args.vrf_items > 0:
+        bench_vrf(args.vrf_items)
 
 
 if __name__ == "__main__":

@@ -33,6 +33,7 @@ from .api import (  # noqa: F401
     PostVerifier,
     ProveOpts,
     SealReport,
+    Status,
     VerifyOpts,
     check_seal,
     init_proof_assemble,
@@ -52,7 +53,7 @@ from .api import (  # noqa: F401
 __all__ = [
     "AuditOpts", "AuditReport", "BatchingVerifier", "Engine", "EngineError", "HealOpts", "HealReport", "OffloadingVerifier", "PostConfig", "PostProof",
     "PostProofMetadata", "PostSetupManager", "PostSetupOpts", "PostVerifier",
-    "ProveOpts", "SealReport", "VerifyOpts", "check_seal", "events",
+    "ProveOpts", "SealReport", "Status", "VerifyOpts", "check_seal", "events",
     "InitProofReport", "InitialProofOpts", "init_proof_assemble",
     "load_engine", "prove_checked", "prove_healed", "repair_data",
     "sample_indices", "seal_assemble", "seal_data",

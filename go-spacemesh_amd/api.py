@@ -203,6 +203,14 @@ def load_engine() -> ctypes.CDLL:
                 POINTER(c_int), POINTER(c_uint32)]),
             "post_verify_vrf_nonce": (c_int, [POINTER(CProofMetadata),
                                               c_uint64, c_uint32, c_uint32]),
+            "post_verify_batch_vrf": (c_int, [
+                POINTER(CProof), POINTER(CProofMetadata), c_uint32,
+                POINTER(_CVerifyConfig), ctypes.c_char_p, c_size_t,
+                POINTER(CProofMetadata), POINTER(c_uint64), c_uint32,
+                POINTER(c_int), POINTER(c_uint32), POINTER(c_int)]),
+            "post_verify_vrf_nonce_batch": (c_int, [
+                POINTER(CProofMetadata), POINTER(c_uint64), c_uint32,
+                c_uint32, c_uint32, POINTER(c_int)]),
             "post_verify_data_sample": (c_int, [
                 c_uint64, c_uint64, c_uint64, c_uint64, c_uint64,
                 POINTER(c_uint64), c_uint32, POINTER(c_uint32)]),
@@ -252,6 +260,9 @@ def load_engine() -> ctypes.CDLL:
                 ctypes.c_char_p, c_uint64, ctypes.c_char_p, ctypes.c_char_p,
                 POINTER(c_uint64), c_uint32, POINTER(c_uint32), c_uint32,
                 c_uint32, ctypes.c_char_p]),
+            "post_selftest_vrf_pred": (c_int, [
+                ctypes.c_char_p, c_uint64, ctypes.c_char_p, c_uint32,
+                POINTER(c_uint32), c_uint32, c_uint32, ctypes.c_char_p]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(lib, name)
@@ -464,6 +475,22 @@ class Engine:
             labels, count, b"".join(keys), bytes(halves),
             (c_uint64 * n)(*difficulties), n,
             (c_uint32 * count)(*task_proof), max_blocks, provider_id, out)
+        self._check(rc)
+        return out.raw[:count]
+
+    def selftest_vrf_pred(self, labels: bytes, thresholds, task_thr,
+                          max_blocks: int = 0, provider_id: int = 0) -> bytes:
+        """The VRF-nonce device predicate over caller-made full labels: one
+        pass byte per task.  thresholds are 32-byte big-endian values,
+        task_thr maps each 32-byte label to its threshold."""
+        count, n = len(labels) // FULL_LABEL_SIZE, len(thresholds)
+        assert len(labels) == count * FULL_LABEL_SIZE
+        assert all(len(t) == FULL_LABEL_SIZE for t in thresholds)
+        assert len(task_thr) == count
+        out = ctypes.create_string_buffer(max(count, 1))
+        rc = self.lib.post_selftest_vrf_pred(
+            labels, count, b"".join(thresholds), n,
+            (c_uint32 * count)(*task_thr), max_blocks, provider_id, out)
         self._check(rc)
         return out.raw[:count]
 
@@ -940,16 +967,51 @@ class PostVerifier:
             cms[i] = m.to_c()
         return cps, cms, n
 
+    @staticmethod
+    def marshal_vrf(metas, indices):
+        """The C argument arrays of the VRF items of verify_batch(vrf=) and
+        verify_vrf_nonce_batch; pass the result in place of (metas,
+        indices) to marshal once."""
+        n = len(metas)
+        assert len(indices) == n
+        cms = (CProofMetadata * n)()
+        for i, m in enumerate(metas):
+            cms[i] = m.to_c()
+        return cms, (c_uint64 * n)(*indices), n
+
+    @staticmethod
+    def _vrf_args(vrf):
+        if len(vrf) == 3:
+            return vrf
+        return PostVerifier.marshal_vrf(*vrf)
+
     def verify_batch(self, proofs, metas, opts: VerifyOpts = VerifyOpts(),
-                     seeds=None, marshalled=None):
+                     seeds=None, marshalled=None, vrf=None):
         # seeds (optional): equal-length per-proof subset seeds — each
         # gossip verify samples with its own peer seed
         # (validation.go:206-209).
+        # vrf (optional): (metas, indices) of VRF-nonce checks that share
+        # the label launch of the proofs; the return value is then
+        # (proof results, [Status per VRF item]).  proofs may be empty.
         vc, _seed = self._vc(opts)
         cps, cms, n = (marshalled if marshalled is not None
                        else self.marshal_batch(proofs, metas))
         statuses = (c_int * n)()
         invs = (c_uint32 * n)()
+        if vrf is not None:
+            vms, vidx, nv = self._vrf_args(vrf)
+            blob, slen = None, 0
+            if seeds is not None:
+                assert len(seeds) == n
+                slen = len(seeds[0]) if n else 0
+                assert all(len(x) == slen for x in seeds)
+                blob = b"".join(seeds) if n else None
+            vst = (c_int * nv)()
+            self.engine._check(self.engine.lib.post_verify_batch_vrf(
+                cps, cms, n, byref(vc), blob, slen, vms, vidx, nv,
+                statuses, invs, vst))
+            return ([(Status(statuses[i]), invs[i]) for i in range(n)],
+                    [Status(vst[j]) for j in range(nv)])
         if seeds is not None:
             assert len(seeds) == n and n > 0
             slen = len(seeds[0])
@@ -967,6 +1029,23 @@ class PostVerifier:
         rc = self.engine.lib.post_verify_vrf_nonce(byref(meta.to_c()), index,
                                                    self.scrypt_n, provider_id)
         self.engine._check(rc)
+
+    def verify_vrf_nonce_batch(self, metas, indices,
+                               provider_id: int = 0) -> list:
+        """One Status per (meta, index): OK, INVALID_INDEX (the label is
+        not below the threshold) or INVALID_ARGS (num_labels == 0), from one
+        label launch.  Nothing is raised for a failing item."""
+        vms, vidx, nv = self.marshal_vrf(metas, indices)
+        return self.verify_vrf_nonce_batch_marshalled((vms, vidx, nv),
+                                                      provider_id)
+
+    def verify_vrf_nonce_batch_marshalled(self, marshalled,
+                                          provider_id: int = 0) -> list:
+        vms, vidx, nv = marshalled
+        vst = (c_int * nv)()
+        self.engine._check(self.engine.lib.post_verify_vrf_nonce_batch(
+            vms, vidx, nv, self.scrypt_n, provider_id, vst))
+        return [Status(vst[j]) for j in range(nv)]
 
 
 # ------------------------- postdata audit -------------------------

@@ -142,6 +142,9 @@ struct VerifyWorkspace {
   DevBuf<uint64_t> d_vdiff;
   size_t proofs_cap = 0;
   DevBuf<uint8_t> d_pass; /* per task, with tasks_cap */
+  DevBuf<uint8_t> d_vthr; /* 32-B VRF threshold per VRF item */
+  DevBuf<uint32_t> d_vmap; /* VRF task -> threshold slot */
+  size_t vrf_cap = 0;
 };
 std::mutex g_vws_mu;
 std::map<int, VerifyWorkspace *> g_vws;
@@ -156,7 +159,15 @@ VerifyWorkspace *get_verify_ws(int dev) {
 }
 
 /* growing a group releases all of it first, then allocates */
-int ws_reserve_proofs(VerifyWorkspace *w, size_t proofs) {
+int ws_reserve_proofs(VerifyWorkspace *w, size_t proofs, size_t vrf_items) {
+  if (vrf_items > w->vrf_cap) {
+    size_t cap = std::max<size_t>(vrf_items, 1024);
+    w->d_vthr.reset(); w->d_vmap.reset();
+    w->vrf_cap = 0;
+    HIP_TRY(w->d_vthr.alloc(cap * 32));
+    HIP_TRY(w->d_vmap.alloc(cap * 4));
+    w->vrf_cap = cap;
+  }
   if (proofs > w->proofs_cap) {
     size_t cap = std::max<size_t>(proofs, 1024);
     w->d_vrk.reset(); w->d_half.reset(); w->d_vdiff.reset();
@@ -3797,26 +3808,27 @@ int post_verify_batch(const PostProof *proofs, const PostProofMetadata *metas,
                                   statuses, invalid_indices);
 }
 
-int post_verify_batch_seeded(const PostProof *proofs,
-                             const PostProofMetadata *metas, uint32_t n,
-                             const PostVerifyConfig *cfg,
-                             const uint8_t *subset_seeds, size_t seed_len,
-                             int *statuses, uint32_t *invalid_indices) {
-  if (!proofs || !metas || !cfg || !statuses) return POST_ERR_INVALID_ARGS;
-  if (cfg->pow_mode != POST_POW_MODE_BLAKE3) {
-    set_error("RandomX k2pow is not supported (use POST_POW_MODE_BLAKE3)");
-    return POST_ERR_UNSUPPORTED;
-  }
-  int rc = require_gpu(cfg->provider_id);
-  if (rc != POST_OK) return rc;
-
+/* The batch behind every verification entry, after validation and
+ * require_gpu: n proofs and n_vrf VRF items (either may be 0) in one label
+ * launch.  Proof tasks come first, in proof order; the VRF items that reach
+ * the device follow, item j under commitment slot n + j and threshold slot
+ * j.  A VRF item with num_labels == 0 gets POST_ERR_INVALID_ARGS and no
+ * task. */
+static int verify_core(const PostProof *proofs, const PostProofMetadata *metas,
+                       uint32_t n, const PostVerifyConfig *cfg,
+                       const uint8_t *subset_seeds, size_t seed_len,
+                       const PostProofMetadata *vrf_metas,
+                       const uint64_t *vrf_indices, uint32_t n_vrf,
+                       int *statuses, uint32_t *invalid_indices,
+                       int *vrf_statuses) {
+  int rc = POST_OK;
   struct Task {
     uint64_t label_index;
     uint32_t proof;
     uint32_t position; /* position within the proof's k2 indices */
   };
   std::vector<Task> tasks;
-  std::vector<uint32_t> commit_words((size_t)n * 8);
+  std::vector<uint32_t> commit_words(((size_t)n + n_vrf) * 8);
   std::vector<std::vector<uint64_t>> proof_indices(n);
   std::vector<std::vector<Task>> per_proof_tasks(n);
   /* position of a proof's first out-of-range index among the positions
@@ -3889,12 +3901,24 @@ int post_verify_batch_seeded(const PostProof *proofs,
       per_proof_tasks[p].push_back({li, p, pos});
     }
   };
-  {
+  /* a VRF item's prep: its commitment into slot n + j */
+  auto vrf_prep_one = [&](uint32_t j) {
+    const PostProofMetadata &me = vrf_metas[j];
+    if ((uint64_t)me.num_units * me.labels_per_unit == 0) {
+      vrf_statuses[j] = POST_ERR_INVALID_ARGS;
+      return;
+    }
+    vrf_statuses[j] = POST_OK;
+    uint8_t cm[32];
+    poste::commitment(me.node_id, me.commitment_atx_id, cm);
+    std::memcpy(commit_words.data() + ((size_t)n + j) * 8, cm, 32);
+  };
+  auto for_each_item = [](uint32_t count, auto &&one) {
     unsigned hw = std::thread::hardware_concurrency();
     unsigned nthreads = std::min<unsigned>(hw ? hw : 1, 32);
-    if (n < 64) nthreads = 1; /* not worth spawning for small batches */
+    if (count < 64) nthreads = 1; /* not worth spawning for small batches */
     if (nthreads <= 1) {
-      for (uint32_t p = 0; p < n; p++) prep_one(p);
+      for (uint32_t p = 0; p < count; p++) one(p);
     } else {
       std::vector<std::thread> ths;
       std::atomic<uint32_t> next{0};
@@ -3902,14 +3926,16 @@ int post_verify_batch_seeded(const PostProof *proofs,
         ths.emplace_back([&] {
           for (;;) {
             uint32_t p = next.fetch_add(64);
-            if (p >= n) return;
-            uint32_t e = std::min(n, p + 64);
-            for (; p < e; p++) prep_one(p);
+            if (p >= count) return;
+            uint32_t e = std::min(count, p + 64);
+            for (; p < e; p++) one(p);
           }
         });
       for (auto &th : ths) th.join();
     }
-  }
+  };
+  for_each_item(n, prep_one);
+  for_each_item(n_vrf, vrf_prep_one);
   /* concatenate in proof order (deterministic task->index mapping) */
   for (uint32_t p = 0; p < n; p++) {
     if (statuses[p] != POST_OK) continue;
@@ -3923,7 +3949,14 @@ int post_verify_batch_seeded(const PostProof *proofs,
       if (invalid_indices) invalid_indices[p] = oor_position[p];
     }
   };
-  if (tasks.empty()) {
+  /* VRF items that go to the device, in item order */
+  std::vector<uint32_t> vrf_items;
+  vrf_items.reserve(n_vrf);
+  for (uint32_t j = 0; j < n_vrf; j++)
+    if (vrf_statuses[j] == POST_OK) vrf_items.push_back(j);
+  const size_t n_ptasks = tasks.size();
+  const size_t n_tasks = n_ptasks + vrf_items.size();
+  if (n_tasks == 0) {
     apply_out_of_range();
     return POST_OK;
   }
@@ -3943,14 +3976,18 @@ int post_verify_batch_seeded(const PostProof *proofs,
     return POST_ERR_OOM;
   }
 
-  std::vector<uint64_t> h_idx(tasks.size());
-  std::vector<uint32_t> h_cid(tasks.size());
-  for (size_t i = 0; i < tasks.size(); i++) {
+  std::vector<uint64_t> h_idx(n_tasks);
+  std::vector<uint32_t> h_cid(n_tasks);
+  for (size_t i = 0; i < n_ptasks; i++) {
     h_idx[i] = tasks[i].label_index;
     h_cid[i] = tasks[i].proof;
   }
+  for (size_t k = 0; k < vrf_items.size(); k++) {
+    h_idx[n_ptasks + k] = vrf_indices[vrf_items[k]];
+    h_cid[n_ptasks + k] = n + vrf_items[k];
+  }
   uint64_t lanes = std::min<uint64_t>(
-      max_lanes, ((tasks.size() + 127) / 128) * 128);
+      max_lanes, ((n_tasks + 127) / 128) * 128);
 
   /* per-proof cipher data for the device predicate (absolute indexing:
    * every proof gets a slot, matching task_proof).  Declared here,
@@ -3973,11 +4010,22 @@ int post_verify_batch_seeded(const PostProof *proofs,
       vdiff[p] = poste::proving_difficulty(cfg->k1, num_labels);
     }
   };
+  /* per-item VRF thresholds, computed beside cipher_prep */
+  std::vector<uint8_t> vthr((size_t)n_vrf * 32, 0);
+  auto vrf_threshold_prep = [&] {
+    for (uint32_t j : vrf_items) {
+      const PostProofMetadata &me = vrf_metas[j];
+      poste::vrf_difficulty((uint64_t)me.num_units * me.labels_per_unit,
+                            vthr.data() + (size_t)j * 32);
+    }
+  };
   DeviceTables tbl;
-  rc = get_aes_tables((int)cfg->provider_id, tbl);
-  if (rc != POST_OK) return rc;
+  if (n_ptasks) {
+    rc = get_aes_tables((int)cfg->provider_id, tbl);
+    if (rc != POST_OK) return rc;
+  }
 
-  std::vector<uint8_t> h_pass(tasks.size());
+  std::vector<uint8_t> h_pass(n_tasks);
   const bool dbg = getenv("POST_VERIFY_DEBUG") != nullptr;
   auto tick = [] {
     return std::chrono::duration<double>(
@@ -3988,12 +4036,13 @@ int post_verify_batch_seeded(const PostProof *proofs,
   {
     VerifyWorkspace *ws = get_verify_ws((int)cfg->provider_id);
     std::lock_guard<std::mutex> lk(ws->mu);
-    rc = ws_reserve(ws, (size_t)lanes * per_lane, tasks.size(),
+    rc = ws_reserve(ws, (size_t)lanes * per_lane, n_tasks,
                     commit_words.size());
     if (rc != POST_OK) return rc;
     if (dbg) {
-      std::fprintf(stderr, "[verify] reserve %.3fs (tasks=%zu lanes=%llu)\n",
-                   tick() - t0, tasks.size(), (unsigned long long)lanes);
+      std::fprintf(stderr,
+                   "[verify] reserve %.3fs (tasks=%zu lanes=%llu vrf=%u)\n",
+                   tick() - t0, n_tasks, (unsigned long long)lanes, n_vrf);
       t0 = tick();
     }
     HIP_TRY(hipMemcpy(ws->d_idx.get(), h_idx.data(), h_idx.size() * 8,
@@ -4015,7 +4064,7 @@ int post_verify_batch_seeded(const PostProof *proofs,
     la.indices = h_idx.size() ? ws->d_idx.get() : nullptr;
     la.commit_ids = ws->d_cid.get();
     la.commitments = ws->d_cm.get();
-    la.count = tasks.size();
+    la.count = n_tasks;
     if (dbg) {
       std::fprintf(stderr, "[verify] h2d %.3fs\n", tick() - t0);
       t0 = tick();
@@ -4023,34 +4072,56 @@ int post_verify_batch_seeded(const PostProof *proofs,
     HIP_TRY(poste_launch_label_kernel(&la, (uint32_t)(lanes / 64),
                                       nullptr));
     cipher_prep(); /* overlaps the label kernel (launch is async) */
+    vrf_threshold_prep();
     if (dbg) {
       (void)hipDeviceSynchronize();
       std::fprintf(stderr, "[verify] label kernel %.3fs\n", tick() - t0);
       t0 = tick();
     }
-    /* device-side AES threshold predicate over the recomputed labels */
-    rc = ws_reserve_proofs(ws, n);
+    rc = ws_reserve_proofs(ws, n_ptasks ? n : 0, vrf_items.empty() ? 0 : n_vrf);
     if (rc != POST_OK) return rc;
-    HIP_TRY(hipMemcpy(ws->d_vrk.get(), vrk.data(), vrk.size() * 4,
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->d_half.get(), vhalf.data(), vhalf.size(),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->d_vdiff.get(), vdiff.data(), vdiff.size() * 8,
-                      hipMemcpyHostToDevice));
-    VerifyPredArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    pa.labels2 = (const uint4 *)ws->d_out.get();
-    pa.count = tasks.size();
-    pa.te = tbl.d_te;
-    pa.sbox = tbl.d_sbox;
-    pa.rk = ws->d_vrk.get();
-    pa.task_proof = ws->d_cid.get(); /* task->proof map doubles as commit id */
-    pa.half = ws->d_half.get();
-    pa.difficulty = ws->d_vdiff.get();
-    pa.pass = ws->d_pass.get();
-    uint32_t pblocks = (uint32_t)std::min<uint64_t>(
-        (tasks.size() + THREADS - 1) / THREADS, VERIFY_PRED_MAX_BLOCKS);
-    HIP_TRY(poste_launch_verify_pred_kernel(&pa, pblocks, nullptr));
+    if (n_ptasks) {
+      /* device-side AES threshold predicate over the recomputed labels */
+      HIP_TRY(hipMemcpy(ws->d_vrk.get(), vrk.data(), vrk.size() * 4,
+                        hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(ws->d_half.get(), vhalf.data(), vhalf.size(),
+                        hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(ws->d_vdiff.get(), vdiff.data(), vdiff.size() * 8,
+                        hipMemcpyHostToDevice));
+      VerifyPredArgs pa;
+      std::memset(&pa, 0, sizeof(pa));
+      pa.labels2 = (const uint4 *)ws->d_out.get();
+      pa.count = n_ptasks;
+      pa.te = tbl.d_te;
+      pa.sbox = tbl.d_sbox;
+      pa.rk = ws->d_vrk.get();
+      pa.task_proof = ws->d_cid.get(); /* task->proof map doubles as commit id */
+      pa.half = ws->d_half.get();
+      pa.difficulty = ws->d_vdiff.get();
+      pa.pass = ws->d_pass.get();
+      uint32_t pblocks = (uint32_t)std::min<uint64_t>(
+          (n_ptasks + THREADS - 1) / THREADS, VERIFY_PRED_MAX_BLOCKS);
+      HIP_TRY(poste_launch_verify_pred_kernel(&pa, pblocks, nullptr));
+    }
+    if (!vrf_items.empty()) {
+      /* the VRF predicate over the tail of the same label buffer; the
+       * threshold table has a slot per ITEM (skipped items leave unused
+       * zero slots) and the map carries each task's item number */
+      HIP_TRY(hipMemcpy(ws->d_vthr.get(), vthr.data(), vthr.size(),
+                        hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(ws->d_vmap.get(), vrf_items.data(),
+                        vrf_items.size() * 4, hipMemcpyHostToDevice));
+      VrfPredArgs va;
+      std::memset(&va, 0, sizeof(va));
+      va.labels2 = (const uint4 *)ws->d_out.get() + 2 * n_ptasks;
+      va.count = vrf_items.size();
+      va.thresholds = (const uint4 *)ws->d_vthr.get();
+      va.task_thr = ws->d_vmap.get();
+      va.pass = ws->d_pass.get() + n_ptasks;
+      uint32_t vblocks = (uint32_t)std::min<uint64_t>(
+          (vrf_items.size() + THREADS - 1) / THREADS, VERIFY_PRED_MAX_BLOCKS);
+      HIP_TRY(poste_launch_vrf_pred_kernel(&va, vblocks, nullptr));
+    }
     HIP_TRY(hipDeviceSynchronize());
     if (dbg) {
       std::fprintf(stderr, "[verify] predicate %.3fs\n", tick() - t0);
@@ -4061,7 +4132,7 @@ int post_verify_batch_seeded(const PostProof *proofs,
   }
 
   /* collect per-proof verdicts from the device predicate */
-  for (size_t i = 0; i < tasks.size(); i++) {
+  for (size_t i = 0; i < n_ptasks; i++) {
     const Task &t = tasks[i];
     if (statuses[t.proof] != POST_OK) continue;
     if (!h_pass[i]) {
@@ -4070,7 +4141,64 @@ int post_verify_batch_seeded(const PostProof *proofs,
     }
   }
   apply_out_of_range();
+  for (size_t k = 0; k < vrf_items.size(); k++)
+    if (!h_pass[n_ptasks + k])
+      vrf_statuses[vrf_items[k]] = POST_ERR_INVALID_INDEX;
   return POST_OK;
+}
+
+int post_verify_batch_seeded(const PostProof *proofs,
+                             const PostProofMetadata *metas, uint32_t n,
+                             const PostVerifyConfig *cfg,
+                             const uint8_t *subset_seeds, size_t seed_len,
+                             int *statuses, uint32_t *invalid_indices) {
+  if (!proofs || !metas || !cfg || !statuses) return POST_ERR_INVALID_ARGS;
+  if (cfg->pow_mode != POST_POW_MODE_BLAKE3) {
+    set_error("RandomX k2pow is not supported (use POST_POW_MODE_BLAKE3)");
+    return POST_ERR_UNSUPPORTED;
+  }
+  int rc = require_gpu(cfg->provider_id);
+  if (rc != POST_OK) return rc;
+  return verify_core(proofs, metas, n, cfg, subset_seeds, seed_len, nullptr,
+                     nullptr, 0, statuses, invalid_indices, nullptr);
+}
+
+int post_verify_batch_vrf(const PostProof *proofs,
+                          const PostProofMetadata *metas, uint32_t n,
+                          const PostVerifyConfig *cfg,
+                          const uint8_t *subset_seeds, size_t seed_len,
+                          const PostProofMetadata *vrf_metas,
+                          const uint64_t *vrf_indices, uint32_t n_vrf,
+                          int *statuses, uint32_t *invalid_indices,
+                          int *vrf_statuses) {
+  if (!cfg) return POST_ERR_INVALID_ARGS;
+  if (n > 0 && (!proofs || !metas || !statuses)) return POST_ERR_INVALID_ARGS;
+  if (n_vrf > 0 && (!vrf_metas || !vrf_indices || !vrf_statuses))
+    return POST_ERR_INVALID_ARGS;
+  if (n > 0 && cfg->pow_mode != POST_POW_MODE_BLAKE3) {
+    set_error("RandomX k2pow is not supported (use POST_POW_MODE_BLAKE3)");
+    return POST_ERR_UNSUPPORTED;
+  }
+  if (n == 0 && n_vrf == 0) return POST_OK;
+  int rc = require_gpu(cfg->provider_id);
+  if (rc != POST_OK) return rc;
+  return verify_core(proofs, metas, n, cfg, subset_seeds, seed_len, vrf_metas,
+                     vrf_indices, n_vrf, statuses, invalid_indices,
+                     vrf_statuses);
+}
+
+int post_verify_vrf_nonce_batch(const PostProofMetadata *metas,
+                                const uint64_t *indices, uint32_t n,
+                                uint32_t scrypt_n, uint32_t provider_id,
+                                int *statuses) {
+  PostVerifyConfig cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  cfg.selected_index = -1;
+  cfg.pow_mode = POST_POW_MODE_BLAKE3;
+  cfg.scrypt_n = scrypt_n;
+  cfg.provider_id = provider_id;
+  return post_verify_batch_vrf(nullptr, nullptr, 0, &cfg, nullptr, 0, metas,
+                               indices, n, nullptr, nullptr, statuses);
 }
 
 int post_verify(const PostProof *proof, const PostProofMetadata *meta,
@@ -4086,43 +4214,15 @@ int post_verify(const PostProof *proof, const PostProofMetadata *meta,
 int post_verify_vrf_nonce(const PostProofMetadata *meta, uint64_t index,
                           uint32_t scrypt_n, uint32_t provider_id) {
   if (!meta) return POST_ERR_INVALID_ARGS;
-  int rc = require_gpu(provider_id);
+  int status = POST_OK;
+  int rc = post_verify_vrf_nonce_batch(meta, &index, 1, scrypt_n, provider_id,
+                                       &status);
   if (rc != POST_OK) return rc;
-  uint64_t num_labels = (uint64_t)meta->num_units * meta->labels_per_unit;
-  uint8_t cm[32];
-  poste::commitment(meta->node_id, meta->commitment_atx_id, cm);
-
-  uint32_t gap_shift = pick_gap_shift(scrypt_n);
-  uint64_t per_lane = ((uint64_t)scrypt_n >> gap_shift) * 128;
-  DevBuf<uint32_t> d_scratch, d_xbuf1;
-  DevBuf<uint64_t> d_idx;
-  DevBuf<uint8_t> d_out;
-  HIP_TRY(d_scratch.alloc((size_t)128 * per_lane));
-  HIP_TRY(d_idx.alloc(8));
-  HIP_TRY(d_out.alloc(32));
-  HIP_TRY(d_xbuf1.alloc(128));
-  HIP_TRY(hipMemcpy(d_idx.get(), &index, 8, hipMemcpyHostToDevice));
-  LabelKernelArgs la;
-  std::memset(&la, 0, sizeof(la));
-  load_commitment_words(cm, la.commitment_le);
-  la.scrypt_n = scrypt_n;
-  la.gap_shift = gap_shift;
-  la.xbuf = d_xbuf1.get();
-  la.out_full = 1;
-  la.scratch = d_scratch.get();
-  la.scratch_lanes = 128;
-  la.out = d_out.get();
-  la.indices = d_idx.get();
-  la.count = 1;
-  HIP_TRY(poste_launch_label_kernel(&la, 1, nullptr));
-  HIP_TRY(hipDeviceSynchronize());
-  uint8_t full[32];
-  HIP_TRY(hipMemcpy(full, d_out.get(), 32, hipMemcpyDeviceToHost));
-  uint8_t difficulty[32];
-  poste::vrf_difficulty(num_labels, difficulty);
-  if (std::memcmp(full, difficulty, 32) < 0) return POST_OK;
-  set_error("vrf nonce label above threshold");
-  return POST_ERR_INVALID_INDEX;
+  if (status == POST_ERR_INVALID_INDEX)
+    set_error("vrf nonce label above threshold");
+  else if (status == POST_ERR_INVALID_ARGS)
+    set_error("vrf nonce: num_units * labels_per_unit is zero");
+  return status;
 }
 
 /* ------------------------- self-test exports ------------------------- */
@@ -4203,6 +4303,51 @@ int post_selftest_verify_pred(const uint8_t *labels, uint64_t count,
       (count + THREADS - 1) / THREADS,
       max_blocks ? max_blocks : VERIFY_PRED_MAX_BLOCKS);
   HIP_TRY(poste_launch_verify_pred_kernel(&pa, pblocks, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(pass, d_pass.get(), (size_t)count, hipMemcpyDeviceToHost));
+  return POST_OK;
+}
+
+int post_selftest_vrf_pred(const uint8_t *labels, uint64_t count,
+                           const uint8_t *thresholds, uint32_t n_thr,
+                           const uint32_t *task_thr, uint32_t max_blocks,
+                           uint32_t provider_id, uint8_t *pass) {
+  if (!labels || !thresholds || !task_thr || !pass || count == 0 ||
+      n_thr == 0)
+    return POST_ERR_INVALID_ARGS;
+  for (uint64_t i = 0; i < count; i++)
+    if (task_thr[i] >= n_thr) {
+      set_error("task_thr entry out of range");
+      return POST_ERR_INVALID_ARGS;
+    }
+  int rc = require_gpu(provider_id);
+  if (rc != POST_OK) return rc;
+
+  DevBuf<uint8_t> d_labels, d_thr, d_pass;
+  DevBuf<uint32_t> d_task_thr;
+  HIP_TRY(d_labels.alloc((size_t)count * 32));
+  HIP_TRY(d_thr.alloc((size_t)n_thr * 32));
+  HIP_TRY(d_task_thr.alloc((size_t)count * 4));
+  HIP_TRY(d_pass.alloc((size_t)count));
+  HIP_TRY(hipMemcpy(d_labels.get(), labels, (size_t)count * 32,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_thr.get(), thresholds, (size_t)n_thr * 32,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_task_thr.get(), task_thr, (size_t)count * 4,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_pass.get(), 0xEE, (size_t)count)); /* neither verdict */
+
+  VrfPredArgs va;
+  std::memset(&va, 0, sizeof(va));
+  va.labels2 = (const uint4 *)d_labels.get();
+  va.count = count;
+  va.thresholds = (const uint4 *)d_thr.get();
+  va.task_thr = d_task_thr.get();
+  va.pass = d_pass.get();
+  uint32_t vblocks = (uint32_t)std::min<uint64_t>(
+      (count + THREADS - 1) / THREADS,
+      max_blocks ? max_blocks : VERIFY_PRED_MAX_BLOCKS);
+  HIP_TRY(poste_launch_vrf_pred_kernel(&va, vblocks, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(pass, d_pass.get(), (size_t)count, hipMemcpyDeviceToHost));
   return POST_OK;

@@ -126,6 +126,17 @@ struct VerifyPredArgs {
   uint8_t *pass;             /* per-task verdict out */
 };
 
+/* VRF-nonce predicate over full labels as the label kernel stores them with
+ * out_full: task t passes when its 32 label bytes, read as one big-endian
+ * number, are strictly below the 32 bytes of threshold slot task_thr[t]. */
+struct VrfPredArgs {
+  const uint4 *labels2;      /* 2 x uint4 per task (full 32-B labels) */
+  uint64_t count;
+  const uint4 *thresholds;   /* 2 x uint4 per slot, big-endian bytes */
+  const uint32_t *task_thr;  /* threshold slot per task */
+  uint8_t *pass;             /* per-task verdict out */
+};
+
 extern "C" {
 hipError_t poste_launch_label_kernel(const LabelKernelArgs *args,
                                      uint32_t blocks, hipStream_t stream);
@@ -145,6 +156,10 @@ hipError_t poste_launch_label_audit(const AuditKernelArgs *args,
 hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
                                            uint32_t blocks,
                                            hipStream_t stream);
+/* grid-stride, POSTE_THREADS per block; hipErrorInvalidValue for an unset
+ * pointer, an empty task list or no block */
+hipError_t poste_launch_vrf_pred_kernel(const VrfPredArgs *args,
+                                        uint32_t blocks, hipStream_t stream);
 hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
                                     uint32_t blocks, hipStream_t stream);
 /* The scan over a resident batch on the caller's stream (init with the

@@ -1210,6 +1210,33 @@ post_verify_pred_kernel(VerifyPredArgs a) {
   }
 }
 
+/* VRF-nonce predicate (verifying.VerifyVRFNonce, validation.go:261-286):
+ * the full label against its item's threshold as 32-byte big-endian
+ * numbers, strictly below.  The words are walked from the last to the
+ * first, so the first word that differs is the one that decides. */
+__global__ void __launch_bounds__(POSTE_THREADS)
+post_vrf_pred_kernel(VrfPredArgs a) {
+  const unsigned long long stride =
+      (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long t =
+           (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+       t < a.count; t += stride) {
+    const uint4 *th = a.thresholds + 2ull * a.task_thr[t];
+    const uint4 l0 = a.labels2[2 * t], l1 = a.labels2[2 * t + 1];
+    const uint4 d0 = th[0], d1 = th[1];
+    const uint32_t lw[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
+    const uint32_t dw[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+    uint32_t below = 0;
+#pragma unroll
+    for (int k = 7; k >= 0; k--) {
+      const uint32_t x = __builtin_bswap32(lw[k]);
+      const uint32_t y = __builtin_bswap32(dw[k]);
+      if (x != y) below = x < y ? 1u : 0u;
+    }
+    a.pass[t] = (uint8_t)below;
+  }
+}
+
 /* Postdata seal: one lane hashes one 1024-label page of the chunk the
  * proving pass has already put on the device.  A page of n
  * labels is n / 4 whole 64-byte blocks and one closing block: the n % 4
@@ -1534,6 +1561,17 @@ hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
   size_t lds = 1024 * 4 + 256;
   hipLaunchKernelGGL(post_verify_pred_kernel, dim3(blocks),
                      dim3(POSTE_THREADS), lds, stream, *args);
+  return hipGetLastError();
+}
+
+hipError_t poste_launch_vrf_pred_kernel(const VrfPredArgs *args,
+                                        uint32_t blocks,
+                                        hipStream_t stream) {
+  if (!args->labels2 || !args->thresholds || !args->task_thr ||
+      !args->pass || args->count == 0 || blocks == 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(post_vrf_pred_kernel, dim3(blocks),
+                     dim3(POSTE_THREADS), 0, stream, *args);
   return hipGetLastError();
 }
 

@@ -167,8 +167,19 @@ class BatchingVerifier:
     the per-peer Subset(k3, seed) of gossip verification
     (validation.go:206-209).
 
-    inner must expose verify_batch(proofs, metas, opts, seeds) — a
-    PostVerifier does."""
+    A VRF-nonce check (verify_vrf_nonce) enters the same queue and the same
+    collector batch: an ATX brings one next to its POST for the same
+    identity (handler_v1.go:133-149), and the engine recomputes both kinds
+    of label in one launch.
+
+    inner must expose verify_batch(proofs, metas, opts, seeds, vrf) — a
+    PostVerifier does.  vrf=(metas, indices) is passed only when the batch
+    holds VRF jobs; the call then returns (proof results, VRF statuses), and
+    proofs, metas are empty and seeds is left out when it holds nothing
+    else.  A batch of proofs alone is called as verify_batch(proofs, metas,
+    seeds=seeds)."""
+
+    _VRF = object()     # in the proof slot of a queued job: a VRF-nonce job
 
     def __init__(self, inner, max_batch: int = 256,
                  max_wait_s: float = 0.002, seed_len: int = 32) -> None:
@@ -205,12 +216,32 @@ class BatchingVerifier:
 
     def _run(self, batch) -> None:
         _metrics.post_verification_queue.set(self._q.qsize())
+        pjobs = [j for j in batch if j[0] is not self._VRF]
+        vjobs = [j for j in batch if j[0] is self._VRF]
         try:
-            res = self._inner.verify_batch(
-                [j[0] for j in batch], [j[1] for j in batch],
-                seeds=[j[2] for j in batch])
-            for (job, (status, inv)) in zip(batch, res):
+            if not vjobs:
+                res = self._inner.verify_batch(
+                    [j[0] for j in pjobs], [j[1] for j in pjobs],
+                    seeds=[j[2] for j in pjobs])
+                vres = []
+            else:
+                vrf = ([j[1] for j in vjobs], [j[2] for j in vjobs])
+                if pjobs:
+                    res, vres = self._inner.verify_batch(
+                        [j[0] for j in pjobs], [j[1] for j in pjobs],
+                        seeds=[j[2] for j in pjobs], vrf=vrf)
+                else:
+                    res, vres = self._inner.verify_batch([], [], vrf=vrf)
+                if len(res) != len(pjobs) or len(vres) != len(vjobs):
+                    raise RuntimeError("verify_batch returned %d + %d "
+                                       "verdicts for %d + %d jobs" % (
+                                           len(res), len(vres), len(pjobs),
+                                           len(vjobs)))
+            for (job, (status, inv)) in zip(pjobs, res):
                 job[3]["status"] = (status, inv)
+                job[4].set()
+            for job, status in zip(vjobs, vres):
+                job[3]["status"] = (status, None)
                 job[4].set()
         except BaseException as e:  # noqa: BLE001
             for job in batch:
@@ -237,6 +268,28 @@ class BatchingVerifier:
         if int(status) != 0:
             from .api import EngineError
             raise EngineError(int(status), f"position {inv}")
+
+    def verify_vrf_nonce(self, meta, index: int) -> None:
+        """Blocking VRF-nonce check through the same batch as the proofs;
+        raises EngineError(INVALID_INDEX) when the label at `index` is not
+        below the threshold, like PostVerifier.verify_vrf_nonce."""
+        if self._closed:
+            raise RuntimeError("verifier closed")
+        import time as _time
+        out: dict = {}
+        done = threading.Event()
+        t0 = _time.monotonic()
+        self._q.put((self._VRF, meta, index, out, done))
+        done.wait()
+        _metrics.post_verification_latency.observe(_time.monotonic() - t0)
+        if "error" in out:
+            raise out["error"]
+        status, _ = out["status"]
+        from .api import EngineError, Status
+        if int(status) != Status.OK:
+            raise EngineError(int(status), "vrf nonce label above threshold"
+                              if int(status) == Status.INVALID_INDEX
+                              else "vrf nonce")
 
     def close(self) -> None:
         self._closed = True

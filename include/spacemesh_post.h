@@ -261,9 +261,49 @@ int post_verify_batch_seeded(const PostProof *proofs,
                              const uint8_t *subset_seeds, size_t seed_len,
                              int *statuses, uint32_t *invalid_indices);
 
-/* verifying.VerifyVRFNonce (validation.go:261-286). */
+/* verifying.VerifyVRFNonce (validation.go:261-286): POST_OK when the full
+ * 32-byte label at `index` is strictly below the VRF threshold of
+ * num_units * labels_per_unit labels as a big-endian number, else
+ * POST_ERR_INVALID_INDEX; POST_ERR_INVALID_ARGS for a NULL meta or
+ * num_units * labels_per_unit == 0.  The index is not range-checked.  It is
+ * the n = 1 case of post_verify_vrf_nonce_batch: the cached per-device
+ * workspace, no allocation per call. */
 int post_verify_vrf_nonce(const PostProofMetadata *meta, uint64_t index,
                           uint32_t scrypt_n, uint32_t provider_id);
+
+/* Proofs and VRF items verified together (an ATX brings both for the same
+ * identity, handler_v1.go:133-149 and :300-324): ONE label-kernel launch
+ * recomputes the sampled labels of all proofs and the label of every VRF
+ * item; the AES predicate runs over the first, the VRF predicate over the
+ * second.  n or n_vrf may be 0 (the arrays of that kind are then not
+ * needed).  statuses / invalid_indices are exactly those of
+ * post_verify_batch_seeded over the proofs alone; vrf_statuses[j] is what
+ * post_verify_vrf_nonce(&vrf_metas[j], vrf_indices[j], cfg->scrypt_n,
+ * cfg->provider_id) returns: POST_OK, POST_ERR_INVALID_INDEX, or
+ * POST_ERR_INVALID_ARGS for num_units * labels_per_unit == 0 (such an item
+ * is not sent to the device and disturbs no other).  The two kinds of
+ * verdict do not depend on each other.
+ * Validated in this order: POST_ERR_INVALID_ARGS for a NULL cfg, for NULL
+ * proofs, metas or statuses with n > 0, for NULL vrf_metas, vrf_indices or
+ * vrf_statuses with n_vrf > 0; POST_ERR_UNSUPPORTED for a non-blake3
+ * pow_mode when n > 0; POST_OK with nothing touched for n == 0 and
+ * n_vrf == 0; then POST_ERR_NO_GPU. */
+int post_verify_batch_vrf(const PostProof *proofs, const PostProofMetadata *metas,
+                          uint32_t n, const PostVerifyConfig *cfg,
+                          const uint8_t *subset_seeds, size_t seed_len,
+                          const PostProofMetadata *vrf_metas,
+                          const uint64_t *vrf_indices, uint32_t n_vrf,
+                          int *statuses, uint32_t *invalid_indices,
+                          int *vrf_statuses);
+
+/* The n == 0 form of post_verify_batch_vrf, for callers with no
+ * PostVerifyConfig at hand: n VRF items in one label launch and one
+ * predicate launch.  POST_ERR_INVALID_ARGS for a NULL array with n > 0,
+ * POST_OK for n == 0, then POST_ERR_NO_GPU. */
+int post_verify_vrf_nonce_batch(const PostProofMetadata *metas,
+                                const uint64_t *indices, uint32_t n,
+                                uint32_t scrypt_n, uint32_t provider_id,
+                                int *statuses);
 
 /* ---------- postdata audit ---------- */
 /* GPU spot-check of on-disk labels: is what is in postdata_*.bin still what
@@ -646,6 +686,20 @@ int post_selftest_verify_pred(const uint8_t *labels, uint64_t count,
                               const uint64_t *difficulties, uint32_t n_proofs,
                               const uint32_t *task_proof, uint32_t max_blocks,
                               uint32_t provider_id, uint8_t *pass);
+
+/* The VRF-nonce device predicate on labels the caller supplies (used only by
+ * tests): `count` full 32-byte labels, `n_thr` 32-byte big-endian
+ * thresholds and `count` task->threshold indices, each below n_thr.  The
+ * production kernel is launched by the production launcher with
+ * min(ceil(count / 256), max_blocks) blocks; max_blocks == 0 is the
+ * production cap (8192).  pass[i] is 1 where label i is strictly below its
+ * threshold as a 32-byte big-endian number, else 0.  An index that is not
+ * below n_thr, a NULL pointer, count == 0 or n_thr == 0 gives
+ * POST_ERR_INVALID_ARGS before a GPU is required. */
+int post_selftest_vrf_pred(const uint8_t *labels, uint64_t count,
+                           const uint8_t *thresholds, uint32_t n_thr,
+                           const uint32_t *task_thr, uint32_t max_blocks,
+                           uint32_t provider_id, uint8_t *pass);
 
 /* version / build info string */
 const char *post_engine_version(void);

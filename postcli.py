@@ -18,7 +18,7 @@ verification, provider listing and benchmarking
         [--check-seal [--max-report N] \
          [--heal [--write-back] [--max-heal-pages N]]]
     python postcli.py verify --datadir DIR --proof proof.json \
-        [--k3 K] [--seed HEX]
+        [--k3 K] [--seed HEX] [--vrf-nonce [INDEX]]
     python postcli.py verify-data --datadir DIR [--every K | --fraction PCT] \
         [--seed S] [--shard R/W | --from I --to J] [--max-report N]
     python postcli.py seal --datadir DIR [--assemble]
@@ -28,6 +28,11 @@ verification, provider listing and benchmarking
 init resumes automatically from existing postdata_*.bin
 (activation/post.go:267-271); --shard R/W initializes only rank R of W
 contiguous index-range shards (the multi-GPU axis).
+
+verify --vrf-nonce also checks the VRF nonce (the Nonce of
+postdata_metadata.json, or INDEX) in the same engine call as the proof and
+adds "vrf_nonce": {"index", "valid"} to the output; exit status 1 when
+either is invalid.
 
 verify-data audits the labels on disk (upstream postcli -verify -fraction):
 one label per window of K labels is recomputed on the GPU and compared with
@@ -375,12 +380,42 @@ def cmd_verify(args):
         md.node_id, md.commitment_atx_id, bytes.fromhex(pj["challenge"]),
         md.num_units, md.labels_per_unit)
     seed = bytes.fromhex(args.seed) if args.seed else None
+    if args.vrf_nonce is not None:
+        return verify_with_vrf_nonce(args, md, ver, proof, meta, seed)
     try:
         ver.verify(proof, meta, gsm_amd.VerifyOpts(subset_seed=seed))
         print(json.dumps({"valid": True}))
     except gsm_amd.EngineError as e:
         print(json.dumps({"valid": False, "error": str(e)}))
         sys.exit(1)
+
+
+def verify_with_vrf_nonce(args, md, ver, proof, meta, seed):
+    """verify --vrf-nonce: the proof and the VRF nonce (the metadata's, or
+    the index given) checked in one engine call."""
+    index = md.nonce if args.vrf_nonce is True else args.vrf_nonce
+    if index is None:
+        raise SystemExit("--vrf-nonce: postdata_metadata.json has no Nonce; "
+                         "give an index")
+    try:
+        res, vres = ver.verify_batch(
+            [proof], [meta], gsm_amd.VerifyOpts(subset_seed=seed),
+            vrf=([meta], [index]))
+    except gsm_amd.EngineError as e:
+        print(json.dumps({"valid": False, "error": str(e)}))
+        return 1
+    (status, inv), vstatus = res[0], vres[0]
+    Status = gsm_amd.Status
+    out = {"valid": int(status) == Status.OK}
+    if int(status) == Status.INVALID_INDEX:
+        out["error"] = str(gsm_amd.EngineError(
+            status, f"invalid POST index at position {inv}"))
+    elif int(status) != Status.OK:
+        out["error"] = str(gsm_amd.EngineError(status, ""))
+    out["vrf_nonce"] = {"index": index,
+                        "valid": int(vstatus) == Status.OK}
+    print(json.dumps(out))
+    return 0 if out["valid"] and out["vrf_nonce"]["valid"] else 1
 
 
 def audit_period(args):
@@ -531,6 +566,10 @@ def build_parser():
     v.add_argument("--k3", type=int, default=37)
     v.add_argument("--seed", default=None)
     v.add_argument("--pow-difficulty", default=None)
+    v.add_argument("--vrf-nonce", nargs="?", type=int, const=True,
+                   default=None, metavar="INDEX",
+                   help="also check the VRF nonce (default: the Nonce of "
+                        "postdata_metadata.json) in the same engine call")
     v.set_defaults(fn=cmd_verify)
     a = sub.add_parser("verify-data")
     a.add_argument("--datadir", required=True)
