@@ -122,6 +122,15 @@ uint64_t prove_chunk_labels() {
   return v < 256 ? 256 : (uint64_t)v;
 }
 
+/* The prove path's scan plan: POST_SCAN_MODE and POST_SCAN_MAX_BLOCKS, read
+ * once per call (tests switch them between calls inside one process); tt4
+ * falls back to bankrep where its LDS opt-in is refused.  The device is
+ * current (require_gpu). */
+hipError_t prove_scan_plan(ScanPlan *plan) {
+  return poste_scan_plan(getenv("POST_SCAN_MODE"),
+                         getenv("POST_SCAN_MAX_BLOCKS"), 1, plan);
+}
+
 /* Cached per-device verification workspace: the worker-pool call pattern
  * (one proof per post_verify call, post_verifier.go:150-160) would
  * otherwise pay scratch/staging allocation on every call.  Calls remain
@@ -362,8 +371,7 @@ struct PostInitSession {
   uint64_t proof_pos = 0;     /* relative position of the part's last marker;
                                  UINT64_MAX while an append is under way */
   uint64_t proof_bytes = 0;   /* size of the part file */
-  int proof_variant = 0;      /* POSTE_SCAN_RESIDENT_* */
-  uint32_t proof_blocks = 0;  /* grid cap */
+  ScanPlan proof_plan{};      /* variant, geometry, grid cap */
   uint32_t proof_hit_cap = 0; /* records per output set */
   ScanKernelArgs proof_scan;  /* tables, round keys, difficulty */
   DevBuf<uint32_t> d_proof_rk;
@@ -1053,8 +1061,7 @@ static int proof_launch(PostInitSession *s, hipStream_t stream, OutputSet &o,
   a.hit_cap = s->proof_hit_cap;
   HIP_TRY(hipMemsetAsync(o.d_hit_count.get(), 0, sizeof(unsigned int), stream));
   if (o.ev_scan[0].get()) HIP_TRY(hipEventRecord(o.ev_scan[0].get(), stream));
-  HIP_TRY(poste_launch_scan_resident(&a, s->proof_variant, s->proof_blocks,
-                                     stream));
+  HIP_TRY(poste_launch_scan(&a, &s->proof_plan, stream));
   if (o.ev_scan[1].get()) HIP_TRY(hipEventRecord(o.ev_scan[1].get(), stream));
   return POST_OK;
 }
@@ -1145,8 +1152,7 @@ static int proof_commit(PostInitSession *s, uint64_t pos, uint64_t count,
                    "hits, %llu batches fetched past the window\n",
                    (unsigned long long)s->proof_timed,
                    (unsigned long long)s->batch,
-                   s->proof_variant == POSTE_SCAN_RESIDENT_TT4 ? "tt4"
-                                                               : "bankrep",
+                   poste_scan_variant_name(s->proof_plan.variant),
                    s->proof_ms / s->proof_timed, s->proof_ms_max, s->proof_ms,
                    (unsigned long long)s->proof_hits,
                    (unsigned long long)s->proof_refetch);
@@ -1224,14 +1230,11 @@ int post_init_enable_proof(PostInitSession *s, const PostProveConfig *cfg) {
   }
   /* POST_INIT_PROOF_SCAN picks the variant, once: bankrep (default) or tt4.
    * Judged before the dir is touched. */
-  int variant = POSTE_SCAN_RESIDENT_BANKREP;
-  if (const char *mode = getenv("POST_INIT_PROOF_SCAN")) {
-    if (std::strcmp(mode, "tt4") == 0) {
-      variant = POSTE_SCAN_RESIDENT_TT4;
-    } else if (*mode && std::strcmp(mode, "bankrep") != 0) {
-      set_error("POST_INIT_PROOF_SCAN must be bankrep or tt4");
-      return POST_ERR_INVALID_ARGS;
-    }
+  const char *mode = getenv("POST_INIT_PROOF_SCAN");
+  if (!mode || !*mode) mode = "bankrep";
+  if (std::strcmp(mode, "tt4") != 0 && std::strcmp(mode, "bankrep") != 0) {
+    set_error("POST_INIT_PROOF_SCAN must be bankrep or tt4");
+    return POST_ERR_INVALID_ARGS;
   }
   s->proof_hdr = h;
   if (s->proof_fd >= 0) (void)::close(s->proof_fd); /* an earlier failed call */
@@ -1285,18 +1288,12 @@ int post_init_enable_proof(PostInitSession *s, const PostProveConfig *cfg) {
   DeviceTables tbl;
   rc = get_aes_tables((int)s->cfg.provider_id, tbl);
   if (rc != POST_OK) return drop(rc);
-  /* POST_SCAN_MAX_BLOCKS lowers the grid cap as on the prove path, read
-   * here and not per launch */
-  s->proof_variant = variant;
+  /* POST_SCAN_MAX_BLOCKS lowers the grid cap as on the prove path; no
+   * fallback: a tt4 that cannot run here is an error */
   {
-    const hipError_t e = poste_scan_resident_prepare(s->proof_variant);
-    if (e != hipSuccess) return drop(hip_fail("poste_scan_resident_prepare", e));
-  }
-  s->proof_blocks =
-      s->proof_variant == POSTE_SCAN_RESIDENT_TT4 ? 2048u : 8192u;
-  if (const char *e = getenv("POST_SCAN_MAX_BLOCKS")) {
-    const long v = strtol(e, nullptr, 10);
-    if (v >= 1 && v < (long)s->proof_blocks) s->proof_blocks = (uint32_t)v;
+    const hipError_t e = poste_scan_plan(mode, getenv("POST_SCAN_MAX_BLOCKS"),
+                                         0, &s->proof_plan);
+    if (e != hipSuccess) return drop(hip_fail("poste_scan_plan", e));
   }
   s->proof_hit_cap =
       proof_hit_capacity(s->batch, cfg->nonces, cfg->k1, total);
@@ -1960,7 +1957,8 @@ static bool seal_on_second_stream() {
  * the disk/host read of chunk i+1 overlaps the device work on chunk i (the
  * 256-GiB config-4 pass never needs the whole label set in host memory).
  * Per chunk it launches the scan (`scan` set: te/sbox/rk/difficulty/hits
- * filled by the caller, labels/count/index_base per chunk here) and/or the
+ * filled by the caller, labels/count/index_base per chunk here, `plan` the
+ * call's scan plan) and/or the
  * seal step (`seal` set).  With no seal step the queue is what it always
  * was: H2D, scan, done[parity].
  *
@@ -1972,7 +1970,8 @@ static bool seal_on_second_stream() {
  * parity, and the last two after the drain: always in page order.  Chunks
  * are a multiple of the page, so no page crosses a chunk. */
 static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
-                          ScanKernelArgs *scan, const SealSink *seal) {
+                          ScanKernelArgs *scan, const ScanPlan *plan,
+                          const SealSink *seal) {
   uint64_t CHUNK = prove_chunk_labels();
   if (seal) CHUNK = (CHUNK + SEAL_PAGE - 1) / SEAL_PAGE * SEAL_PAGE;
   const uint64_t chunk_lab = std::min(CHUNK, num_labels);
@@ -2026,9 +2025,7 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
       scan->labels = (const uint4 *)d_labels[parity].get();
       scan->count = cnt;
       scan->index_base = base;
-      uint32_t blocks = (uint32_t)std::min<uint64_t>(
-          (cnt + THREADS - 1) / THREADS, 8192);
-      HIP_TRY(poste_launch_scan_kernel(scan, blocks, stream));
+      HIP_TRY(poste_launch_scan(scan, plan, stream));
     }
     if (seal) {
       const uint64_t n_pages = (cnt + SEAL_PAGE - 1) / SEAL_PAGE;
@@ -2065,11 +2062,11 @@ static int label_pipeline(const LabelReader &read_labels, uint64_t num_labels,
 
 /* Optional step of prove_core between "hits copied back" and "winner
  * chosen" (post_prove_healed): it may rewrite the hit list, and may launch
- * further scans with the pass's own arguments — tables, round keys,
- * difficulty and hit buffers are still allocated, the hit buffers free for
- * reuse. */
+ * further scans with the pass's own arguments and plan — tables, round
+ * keys, difficulty and hit buffers are still allocated, the hit buffers free
+ * for reuse. */
 using HitHook =
-    std::function<int(const ScanKernelArgs &scan,
+    std::function<int(const ScanKernelArgs &scan, const ScanPlan &plan,
                       std::vector<PostScanHit> &hits)>;
 
 static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
@@ -2092,6 +2089,8 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
   DeviceTables tbl;
   rc = get_aes_tables(dev, tbl);
   if (rc != POST_OK) return rc;
+  ScanPlan plan;
+  HIP_TRY(prove_scan_plan(&plan));
 
   const uint32_t n_ciphers = cfg->nonces / POSTE_NONCES_PER_AES;
   const uint32_t n_groups = cfg->nonces / POSTE_NONCE_GROUP;
@@ -2134,7 +2133,7 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
   sa.hit_count = d_hit_count.get();
   sa.hit_cap = HIT_CAP;
 
-  rc = label_pipeline(read_labels, num_labels, &sa, seal);
+  rc = label_pipeline(read_labels, num_labels, &sa, &plan, seal);
   if (rc != POST_OK) return rc;
   unsigned int n_hits = 0;
   HIP_TRY(hipMemcpy(&n_hits, d_hit_count.get(), 4, hipMemcpyDeviceToHost));
@@ -2148,7 +2147,7 @@ static int prove_core(const LabelReader &read_labels, uint64_t num_labels,
     HIP_TRY(hipMemcpy(all_hits.data(), d_hits.get(),
                       sizeof(PostScanHit) * n_hits, hipMemcpyDeviceToHost));
   if (hook) {
-    rc = (*hook)(sa, all_hits);
+    rc = (*hook)(sa, plan, all_hits);
     if (rc != POST_OK) return rc;
   }
 
@@ -2201,6 +2200,8 @@ int post_prove_scan(const uint8_t *labels, uint64_t count,
   DeviceTables tbl;
   rc = get_aes_tables((int)cfg->provider_id, tbl);
   if (rc != POST_OK) return rc;
+  ScanPlan plan;
+  HIP_TRY(prove_scan_plan(&plan));
 
   const uint32_t n_ciphers = cfg->nonces / POSTE_NONCES_PER_AES;
   std::vector<uint32_t> rk((size_t)n_ciphers * 44);
@@ -2241,9 +2242,7 @@ int post_prove_scan(const uint8_t *labels, uint64_t count,
     sa.labels = (const uint4 *)d_labels.get();
     sa.count = cnt;
     sa.index_base = index_base + base;
-    uint32_t blocks = (uint32_t)std::min<uint64_t>(
-        (cnt + THREADS - 1) / THREADS, 8192);
-    HIP_TRY(poste_launch_scan_kernel(&sa, blocks, nullptr));
+    HIP_TRY(poste_launch_scan(&sa, &plan, nullptr));
     HIP_TRY(hipDeviceSynchronize());
   }
   unsigned int got = 0;
@@ -2468,7 +2467,7 @@ int post_seal_digest_buffer(const uint8_t *labels, uint64_t count,
     std::memcpy(digests + first * SEAL_DIGEST, d, n * SEAL_DIGEST);
     return POST_OK;
   };
-  rc = label_pipeline(reader, count, nullptr, &sink);
+  rc = label_pipeline(reader, count, nullptr, nullptr, &sink);
   if (rc == POST_OK) *n_pages = seal_pages(count);
   return rc;
 }
@@ -2512,7 +2511,7 @@ int post_seal_data(const char *data_dir, uint32_t provider_id,
     set_error("short write to postdata_seal.bin.tmp");
     rc = POST_ERR_IO;
   } else {
-    rc = label_pipeline(dir_reader(files), total, nullptr, &sink);
+    rc = label_pipeline(dir_reader(files), total, nullptr, nullptr, &sink);
   }
   if (rc == POST_OK && (std::fflush(f) != 0 || fsync(fileno(f)) != 0)) {
     set_error("cannot flush postdata_seal.bin.tmp");
@@ -2556,7 +2555,7 @@ int post_check_seal(const char *data_dir, uint32_t provider_id,
   SealSink sink = [&chk](uint64_t first, uint64_t n, const uint8_t *d) {
     return chk.compare(first, n, d);
   };
-  rc = label_pipeline(dir_reader(files), total, nullptr, &sink);
+  rc = label_pipeline(dir_reader(files), total, nullptr, nullptr, &sink);
   if (rc != POST_OK) return rc;
   chk.report(r);
   return POST_OK;
@@ -3286,9 +3285,10 @@ static int heal_regenerate(HealWork &w) {
 }
 
 /* Step 6: the production scan over the compact buffer at index base 0, with
- * the pass's own scan arguments; first-pass hits of bad pages go, the new
- * ones come in under their global indices. */
+ * the pass's own scan arguments and plan; first-pass hits of bad pages go,
+ * the new ones come in under their global indices. */
 static int heal_rescan(HealWork &w, const ScanKernelArgs &pass,
+                       const ScanPlan &plan,
                        const std::vector<bool> &bad_map,
                        std::vector<PostScanHit> &hits) {
   const double t0 = heal_tick();
@@ -3297,9 +3297,7 @@ static int heal_rescan(HealWork &w, const ScanKernelArgs &pass,
   sa.count = w.count;
   sa.index_base = 0;
   HIP_TRY(hipMemset(sa.hit_count, 0, 4));
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>(
-      (w.count + THREADS - 1) / THREADS, 8192);
-  HIP_TRY(poste_launch_scan_kernel(&sa, blocks, nullptr));
+  HIP_TRY(poste_launch_scan(&sa, &plan, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   unsigned int got = 0;
   HIP_TRY(hipMemcpy(&got, sa.hit_count, 4, hipMemcpyDeviceToHost));
@@ -3472,11 +3470,11 @@ int post_prove_healed(const char *data_dir, const PostProveConfig *cfg,
   };
   bool healed = false;
   /* by the time the hook runs the pass is over: chk holds every bad page */
-  HitHook hook = [&](const ScanKernelArgs &scan,
+  HitHook hook = [&](const ScanKernelArgs &scan, const ScanPlan &plan,
                      std::vector<PostScanHit> &hits) -> int {
     if (chk.pages_bad == 0 || chk.pages_bad > limit) return POST_OK;
     int hrc = heal_regenerate(w);
-    if (hrc == POST_OK) hrc = heal_rescan(w, scan, bad_map, hits);
+    if (hrc == POST_OK) hrc = heal_rescan(w, scan, plan, bad_map, hits);
     if (hrc == POST_OK && heal->write_back) hrc = heal_write_back(w);
     if (hrc == POST_OK) healed = true;
     return hrc;
@@ -3530,7 +3528,7 @@ int post_repair_data(const char *data_dir, uint32_t provider_id,
   SealSink sink = [&chk](uint64_t first, uint64_t n, const uint8_t *d) {
     return chk.compare(first, n, d);
   };
-  rc = label_pipeline(dir_reader(files), w.total, nullptr, &sink);
+  rc = label_pipeline(dir_reader(files), w.total, nullptr, nullptr, &sink);
   if (rc != POST_OK) return rc;
   const bool heal_it = chk.pages_bad && chk.pages_bad <= limit;
   if (heal_it) {

@@ -73,6 +73,23 @@ struct ScanKernelArgs {
   uint32_t hit_cap;
 };
 
+/* Which scan kernel runs and with what geometry; made by poste_scan_plan,
+ * the one place that knows a variant's figures, and read by everyone else. */
+enum ScanVariant {
+  POSTE_SCAN_SHARED,       /* shared T-tables + S-box */
+  POSTE_SCAN_BANKREP,      /* bank-replicated Te0 */
+  POSTE_SCAN_BANKREP_BG,   /*   with batched gathers */
+  POSTE_SCAN_BANKREP512,   /*   at 512 threads */
+  POSTE_SCAN_BANKREP512_BG,/*   at 512 threads, batched gathers */
+  POSTE_SCAN_TT4,          /* 4 interleaved bank-replicated tables */
+};
+struct ScanPlan {
+  int variant;         /* ScanVariant */
+  uint32_t threads;    /* per block */
+  uint32_t lds_bytes;  /* dynamic LDS per block */
+  uint32_t max_blocks; /* grid cap, >= 1 */
+};
+
 /* Postdata seal: page p is labels [1024 p, min(1024 (p + 1), count)) of
  * `labels`; digests[p] receives the first 16 bytes of SHA-256 over the
  * page's bytes.  digests holds ceil(count / 1024) entries. */
@@ -160,22 +177,20 @@ hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
  * pointer, an empty task list or no block */
 hipError_t poste_launch_vrf_pred_kernel(const VrfPredArgs *args,
                                         uint32_t blocks, hipStream_t stream);
-hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
-                                    uint32_t blocks, hipStream_t stream);
-/* The scan over a resident batch on the caller's stream (init with the
- * initial proof): the kernels of poste_launch_scan_kernel, no
- * environment read per launch.  prepare is called once per process and
- * variant, outside any stream (tt4: the 128 KiB dynamic-LDS opt-in; an error
- * means the variant cannot run here).  The grid is min(ceil(count /
- * threads), max_blocks) with threads = poste_scan_resident_threads(variant);
- * hipErrorInvalidValue for an unset pointer, an empty batch or no block. */
-#define POSTE_SCAN_RESIDENT_TT4 0
-#define POSTE_SCAN_RESIDENT_BANKREP 1
-hipError_t poste_scan_resident_prepare(int variant);
-uint32_t poste_scan_resident_threads(int variant);
-hipError_t poste_launch_scan_resident(const ScanKernelArgs *args, int variant,
-                                      uint32_t max_blocks,
-                                      hipStream_t stream);
+/* The scan kernel a plan names.  mode is the exact name; NULL means tt4 and
+ * any other string bankrep.  max_blocks, when it parses to a value from 1 up
+ * to the variant's own cap, lowers the cap (NULL: the variant's own).  tt4
+ * needs a 128 KiB dynamic-LDS opt-in, made here, outside any stream: where it
+ * is refused the plan is bankrep's with allow_fallback, the error without.
+ * The environment is the caller's business, read once per C-ABI call. */
+hipError_t poste_scan_plan(const char *mode, const char *max_blocks,
+                           int allow_fallback, ScanPlan *out);
+/* the name poste_scan_plan parses for the variant */
+const char *poste_scan_variant_name(int variant);
+/* on the caller's stream, grid min(ceil(count / threads), max_blocks);
+ * hipErrorInvalidValue for an unset pointer, an empty batch or no block */
+hipError_t poste_launch_scan(const ScanKernelArgs *args, const ScanPlan *plan,
+                             hipStream_t stream);
 /* one lane per page; hipErrorInvalidValue for an empty or unset buffer */
 hipError_t poste_launch_seal_kernel(const SealKernelArgs *args,
                                     hipStream_t stream);

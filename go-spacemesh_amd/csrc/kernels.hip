@@ -10,10 +10,11 @@
  *   in index-list mode for verification's label recompute
  *   (validation.go:182-222 -> K3 sampled indices) with per-task commitments.
  *
- * post_scan_kernel: the proving index scan (post-service GenProof,
+ * post_scan_*_kernel: the proving index scan (post-service GenProof,
  *   api/grpcserver/post_client.go:69-143): AES-128 over each 16-B label for
- *   n_ciphers ciphers (2 nonces per cipher), T-tables + round keys staged in
- *   LDS, passing (nonce,index) pairs appended with a global atomic.
+ *   n_ciphers ciphers (2 nonces per cipher), T-tables staged in LDS by one
+ *   of three table policies, passing (nonce,index) pairs appended with a
+ *   global atomic.
  *
  * post_seal_kernel: the postdata seal: 16 bytes of SHA-256 per
  *   1024-label page of a chunk the proving pass has on the device, one lane
@@ -715,152 +716,71 @@ post_label_audit_tail_kernel(AuditKernelArgs aa) {
   }
 }
 
-/* ------------------------- proving scan kernel ------------------------- */
-/* ScanKernelArgs: see kernel_args.h */
+/* ------------------------- proving scan kernels ------------------------- */
+/* ScanKernelArgs and ScanPlan: see kernel_args.h.
+ *
+ * One AES-128 encryption and one scan body.  The kernels differ in where a
+ * T-table word comes from, which a table policy says: its LDS layout and
+ * fill, te<T>(x) for the word of table T (rot<T> brings it into place where
+ * one table serves all four), sb<S>(x) for the S-box byte of x at bit S, and
+ * whether the scan body copies a cipher's round keys into registers.  Lookups
+ * through the vector L1, all or half of them, measured conclusively worse:
+ * profiles/r02_scan_tt_verdict.md. */
 
-__global__ void __launch_bounds__(POSTE_THREADS)
-post_scan_kernel(ScanKernelArgs a) {
-  /* T-tables + sbox in LDS (random per-lane indices); round keys stay in
-   * global — the cipher loop is wave-uniform, so they compile to scalar
-   * loads through the constant cache instead of ~5.8K extra LDS reads per
-   * label.  The kernel is LDS-conflict-throughput bound (ILP 1/2/4 all
-   * measure ~274 M labels/s; a random 32-lane b32 gather costs
-   * 2 x E[max 32-into-32-bank load] ~ 6.4 LDS cycles — see
-   * profiles/r01_scan_sweep.md and MI355X_MICROARCH.md §LDS).  Two
-   * gated A/B variants attack that wall (both UNVERIFIED on hardware,
-   * round-2 retest):
-   *   POSTE_SCAN_GLOBAL_TT — all lookups through the vector L1;
-   *   POSTE_SCAN_SPLIT_TT — Te0/Te1 from LDS, Te2/Te3 through the L1,
-   *     so the two memory pipes each carry half the gathers. */
-#if defined(POSTE_SCAN_GLOBAL_TT)
-  const uint32_t *TE_LO = a.te; /* Te0/Te1 (offsets 0, 256) */
-  const uint32_t *TE_HI = a.te; /* Te2/Te3 (offsets 512, 768) */
-  const uint8_t *sSbox = a.sbox;
-#elif defined(POSTE_SCAN_SPLIT_TT)
-  extern __shared__ uint32_t lds[];
-  uint32_t *TE_LO = lds;                     /* Te0/Te1: 512 words */
-  const uint32_t *TE_HI = a.te;              /* Te2/Te3 via L1 */
-  uint8_t *sSbox = (uint8_t *)(lds + 512);   /* 256 bytes */
-  for (uint32_t i = threadIdx.x; i < 512; i += blockDim.x) TE_LO[i] = a.te[i];
-  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
-    sSbox[i] = a.sbox[i];
-  __syncthreads();
-#else
-  extern __shared__ uint32_t lds[];
-  uint32_t *sTe = lds;                      /* 1024 words */
-  uint8_t *sSbox = (uint8_t *)(sTe + 1024); /* 256 bytes */
-  uint32_t *TE_LO = sTe, *TE_HI = sTe;
-
-  for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) sTe[i] = a.te[i];
-  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
-    sSbox[i] = a.sbox[i];
-  __syncthreads();
-#endif
-
-  /* Four independent labels per lane (ILP): a single AES chain leaves the
-   * wave ~76% latency-stalled (profiles: SQ_ACTIVE_INST 10%, LDS 14%);
-   * interleaving L chains fills the LDS-latency shadows. */
-  const unsigned long long stride =
-      (unsigned long long)gridDim.x * blockDim.x;
+/* Independent labels (AES chains) per lane.  A single chain leaves the wave
+ * ~76% latency-stalled (profiles: SQ_ACTIVE_INST 10%, LDS 14%); interleaving
+ * chains fills the LDS-latency shadows.  2 chains at 8 waves/SIMD measured
+ * best at 256 and 512 threads.  tt4 runs max(4, POSTE_SCAN_ILP): 4 measured
+ * best there (r2d sweep); at one workgroup per CU there are only 16 waves to
+ * hide latency, so deeper chains pay.  -DPOSTE_SCAN_ILP=n: make scan1/scan4. */
 #ifndef POSTE_SCAN_ILP
-#define POSTE_SCAN_ILP 2 /* 2 chains @ 8 waves/SIMD measured best */
+#define POSTE_SCAN_ILP 2
 #endif
-  constexpr int L = POSTE_SCAN_ILP;
-  const unsigned long long span = stride * L;
-  for (unsigned long long t0 =
-           (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-       t0 < a.count; t0 += span) {
-    uint32_t p[L][4];
-    unsigned long long ts[L];
-#pragma unroll
-    for (int u = 0; u < L; u++) {
-      unsigned long long t = t0 + (unsigned long long)u * stride;
-      ts[u] = t < a.count ? t : t0; /* clamp: duplicates are harmless
-                                       (hits deduped by nonce list merge
-                                       never occur: same index+nonce hits
-                                       only appended for u==0's slot) */
-      uint4 lraw = a.labels[ts[u]];
-      p[u][0] = __builtin_bswap32(lraw.x);
-      p[u][1] = __builtin_bswap32(lraw.y);
-      p[u][2] = __builtin_bswap32(lraw.z);
-      p[u][3] = __builtin_bswap32(lraw.w);
-    }
-    const int live = (int)((a.count - t0 + stride - 1) / stride) < L
-                         ? (int)((a.count - t0 + stride - 1) / stride)
-                         : L;
-    for (uint32_t c = 0; c < a.n_ciphers; c++) {
-      const uint32_t *rk = a.rk + c * 44;
-      uint32_t w[L][4];
-#pragma unroll
-      for (int u = 0; u < L; u++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) w[u][k] = p[u][k] ^ rk[k];
-#pragma unroll
-      for (int r = 1; r < 10; r++) {
-#pragma unroll
-        for (int u = 0; u < L; u++) {
-          uint32_t n0 = TE_LO[w[u][0] >> 24] ^
-                        TE_LO[256 + ((w[u][1] >> 16) & 0xff)] ^
-                        TE_HI[512 + ((w[u][2] >> 8) & 0xff)] ^
-                        TE_HI[768 + (w[u][3] & 0xff)] ^ rk[4 * r];
-          uint32_t n1 = TE_LO[w[u][1] >> 24] ^
-                        TE_LO[256 + ((w[u][2] >> 16) & 0xff)] ^
-                        TE_HI[512 + ((w[u][3] >> 8) & 0xff)] ^
-                        TE_HI[768 + (w[u][0] & 0xff)] ^ rk[4 * r + 1];
-          uint32_t n2 = TE_LO[w[u][2] >> 24] ^
-                        TE_LO[256 + ((w[u][3] >> 16) & 0xff)] ^
-                        TE_HI[512 + ((w[u][0] >> 8) & 0xff)] ^
-                        TE_HI[768 + (w[u][1] & 0xff)] ^ rk[4 * r + 2];
-          uint32_t n3 = TE_LO[w[u][3] >> 24] ^
-                        TE_LO[256 + ((w[u][0] >> 16) & 0xff)] ^
-                        TE_HI[512 + ((w[u][1] >> 8) & 0xff)] ^
-                        TE_HI[768 + (w[u][2] & 0xff)] ^ rk[4 * r + 3];
-          w[u][0] = n0; w[u][1] = n1; w[u][2] = n2; w[u][3] = n3;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < L; u++) {
-        if (u >= live) break;
-        uint32_t f0 = (((uint32_t)sSbox[w[u][0] >> 24] << 24) |
-                       ((uint32_t)sSbox[(w[u][1] >> 16) & 0xff] << 16) |
-                       ((uint32_t)sSbox[(w[u][2] >> 8) & 0xff] << 8) |
-                       sSbox[w[u][3] & 0xff]) ^ rk[40];
-        uint32_t f1 = (((uint32_t)sSbox[w[u][1] >> 24] << 24) |
-                       ((uint32_t)sSbox[(w[u][2] >> 16) & 0xff] << 16) |
-                       ((uint32_t)sSbox[(w[u][3] >> 8) & 0xff] << 8) |
-                       sSbox[w[u][0] & 0xff]) ^ rk[41];
-        uint32_t f2 = (((uint32_t)sSbox[w[u][2] >> 24] << 24) |
-                       ((uint32_t)sSbox[(w[u][3] >> 16) & 0xff] << 16) |
-                       ((uint32_t)sSbox[(w[u][0] >> 8) & 0xff] << 8) |
-                       sSbox[w[u][1] & 0xff]) ^ rk[42];
-        uint32_t f3 = (((uint32_t)sSbox[w[u][3] >> 24] << 24) |
-                       ((uint32_t)sSbox[(w[u][0] >> 16) & 0xff] << 16) |
-                       ((uint32_t)sSbox[(w[u][1] >> 8) & 0xff] << 8) |
-                       sSbox[w[u][2] & 0xff]) ^ rk[43];
-        unsigned long long v0 =
-            __builtin_bswap64(((unsigned long long)f0 << 32) | f1);
-        unsigned long long v1 =
-            __builtin_bswap64(((unsigned long long)f2 << 32) | f3);
-        if (v0 < a.difficulty) {
-          unsigned int s = atomicAdd(a.hit_count, 1u);
-          if (s < a.hit_cap) {
-            a.hits[s].index = a.index_base + ts[u];
-            a.hits[s].nonce = c * POSTE_NONCES_PER_AES;
-          }
-        }
-        if (v1 < a.difficulty) {
-          unsigned int s = atomicAdd(a.hit_count, 1u);
-          if (s < a.hit_cap) {
-            a.hits[s].index = a.index_base + ts[u];
-            a.hits[s].nonce = c * POSTE_NONCES_PER_AES + 1;
-          }
-        }
-      }
-    }
+
+/* Shared tables: Te0..Te3 and the S-box once per workgroup, random per-lane
+ * indices.  LDS-conflict-throughput bound (ILP 1/2/4 all measure ~274 M
+ * labels/s; a random 32-lane b32 gather costs 2 x E[max 32-into-32-bank
+ * load] ~ 6.4 LDS cycles — see profiles/r01_scan_sweep.md and
+ * MI355X_MICROARCH.md §LDS).  Round keys stay in global: the cipher loop is
+ * wave-uniform, so they compile to scalar loads through the constant cache
+ * instead of ~5.8K extra LDS reads per label. */
+struct TeShared {
+  static constexpr uint32_t LDS_BYTES = 1024 * 4 + 256;
+  static constexpr bool RK_IN_REGS = false;
+  const uint32_t *sTe;  /* 1024 words */
+  const uint8_t *sSbox; /* 256 bytes */
+  __device__ __forceinline__ TeShared(uint32_t *lds, const uint32_t *te,
+                                      const uint8_t *sbox) {
+    uint8_t *sb = (uint8_t *)(lds + 1024);
+    for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) lds[i] = te[i];
+    for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) sb[i] = sbox[i];
+    __syncthreads();
+    sTe = lds;
+    sSbox = sb;
   }
+  template <int T>
+  __device__ __forceinline__ uint32_t te(uint32_t x) const {
+    return sTe[T * 256 + x];
+  }
+  template <int T>
+  static __device__ __forceinline__ uint32_t rot(uint32_t g) { return g; }
+  template <int S>
+  __device__ __forceinline__ uint32_t sb(uint32_t x) const {
+    return (uint32_t)sSbox[x] << S;
+  }
+};
+
+/* S-box byte of a Te0 word at bit S: te[x] packs [s2,s,s,s3], so s =
+ * (te[x]>>8)&0xff and the shift folds into the mask. */
+template <int S>
+static __device__ __forceinline__ uint32_t te0_sbox(uint32_t g) {
+  if constexpr (S >= 8)
+    return (g & 0xff00u) << (S - 8);
+  else
+    return (g >> 8) & 0xffu;
 }
 
-/* Bank-replicated scan: one Te0 table replicated across the 32 LDS banks.
+/* Bank-replicated: one Te0 table replicated across the 32 LDS banks.
  * Copy c is strided so element x of copy c sits at word x*32 + c; the bank
  * of word w is w%32 = c, and each lane reads only copy (lane%32), so every
  * ds_read_b32 gather in the cipher loop is conflict-free BY CONSTRUCTION
@@ -871,177 +791,165 @@ post_scan_kernel(ScanKernelArgs a) {
  * 3.2x fewer LDS cycles for 32 KB of LDS per workgroup and a few extra
  * VALU ops — Te1/2/3 derive from Te0 by byte rotation (one v_alignbit
  * each; te[256+x] = ror8(te[x]), crypto_host.cpp:332-334), and the final
- * round's S-box is byte 1 of Te0 (te[x] packs [s2,s,s,s3] so s =
- * (te[x]>>8)&0xff) — no separate sbox table at all. */
-#define ROR8(x) __builtin_amdgcn_alignbit((x), (x), 8)
-#define ROR16(x) __builtin_amdgcn_alignbit((x), (x), 16)
-#define ROR24(x) __builtin_amdgcn_alignbit((x), (x), 24)
-
-template <int THREADS_, bool BATCHG>
-__global__ void __launch_bounds__(THREADS_)
-post_scan_bankrep_kernel(ScanKernelArgs a) {
-  extern __shared__ uint32_t sTe[]; /* 8192 words = 32 copies x 1 KiB */
-  for (uint32_t i = threadIdx.x; i < 8192; i += blockDim.x)
-    sTe[i] = a.te[i >> 5]; /* consecutive lanes -> consecutive banks */
-  __syncthreads();
-  const uint32_t lane31 = threadIdx.x & 31;
-#define TE0R(idx) sTe[(((uint32_t)(idx)) << 5) | lane31]
-
-  const unsigned long long stride =
-      (unsigned long long)gridDim.x * blockDim.x;
-#ifndef POSTE_SCAN_ILP
-#define POSTE_SCAN_ILP 2
-#endif
-  constexpr int L = POSTE_SCAN_ILP;
-  const unsigned long long span = stride * L;
-  for (unsigned long long t0 =
-           (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-       t0 < a.count; t0 += span) {
-    uint32_t p[L][4];
-    unsigned long long ts[L];
-#pragma unroll
-    for (int u = 0; u < L; u++) {
-      unsigned long long t = t0 + (unsigned long long)u * stride;
-      ts[u] = t < a.count ? t : t0; /* clamp: duplicate work, hits only
-                                       recorded for live chains below */
-      uint4 lraw = a.labels[ts[u]];
-      p[u][0] = __builtin_bswap32(lraw.x);
-      p[u][1] = __builtin_bswap32(lraw.y);
-      p[u][2] = __builtin_bswap32(lraw.z);
-      p[u][3] = __builtin_bswap32(lraw.w);
-    }
-    const int live = (int)((a.count - t0 + stride - 1) / stride) < L
-                         ? (int)((a.count - t0 + stride - 1) / stride)
-                         : L;
-    for (uint32_t c = 0; c < a.n_ciphers; c++) {
-      /* expanded key into registers up front: a.rk accesses inside the
-       * round loop compile to per-round VECTOR global loads (wave-uniform
-       * but the compiler cannot prove it) whose vmcnt waits serialize the
-       * cipher loop */
-      uint32_t rk[44];
-#pragma unroll
-      for (int k = 0; k < 44; k++) rk[k] = a.rk[c * 44 + k];
-      uint32_t w[L][4];
-#pragma unroll
-      for (int u = 0; u < L; u++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) w[u][k] = p[u][k] ^ rk[k];
-#pragma unroll
-      for (int r = 1; r < 10; r++) {
-        if (BATCHG) {
-          /* issue all of the round's gathers before any combine: widens
-           * the read->use distance so partial lgkmcnt waits overlap the
-           * whole gather batch with the previous combines */
-          uint32_t g[L][16];
-#pragma unroll
-          for (int u = 0; u < L; u++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-              g[u][4 * q + 0] = TE0R(w[u][q] >> 24);
-              g[u][4 * q + 1] = TE0R((w[u][(q + 1) & 3] >> 16) & 0xff);
-              g[u][4 * q + 2] = TE0R((w[u][(q + 2) & 3] >> 8) & 0xff);
-              g[u][4 * q + 3] = TE0R(w[u][(q + 3) & 3] & 0xff);
-            }
-#pragma unroll
-          for (int u = 0; u < L; u++)
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-              w[u][q] = g[u][4 * q] ^ ROR8(g[u][4 * q + 1]) ^
-                        ROR16(g[u][4 * q + 2]) ^ ROR24(g[u][4 * q + 3]) ^
-                        rk[4 * r + q];
-        } else {
-#pragma unroll
-        for (int u = 0; u < L; u++) {
-          uint32_t n0 = TE0R(w[u][0] >> 24) ^
-                        ROR8(TE0R((w[u][1] >> 16) & 0xff)) ^
-                        ROR16(TE0R((w[u][2] >> 8) & 0xff)) ^
-                        ROR24(TE0R(w[u][3] & 0xff)) ^ rk[4 * r];
-          uint32_t n1 = TE0R(w[u][1] >> 24) ^
-                        ROR8(TE0R((w[u][2] >> 16) & 0xff)) ^
-                        ROR16(TE0R((w[u][3] >> 8) & 0xff)) ^
-                        ROR24(TE0R(w[u][0] & 0xff)) ^ rk[4 * r + 1];
-          uint32_t n2 = TE0R(w[u][2] >> 24) ^
-                        ROR8(TE0R((w[u][3] >> 16) & 0xff)) ^
-                        ROR16(TE0R((w[u][0] >> 8) & 0xff)) ^
-                        ROR24(TE0R(w[u][1] & 0xff)) ^ rk[4 * r + 2];
-          uint32_t n3 = TE0R(w[u][3] >> 24) ^
-                        ROR8(TE0R((w[u][0] >> 16) & 0xff)) ^
-                        ROR16(TE0R((w[u][1] >> 8) & 0xff)) ^
-                        ROR24(TE0R(w[u][2] & 0xff)) ^ rk[4 * r + 3];
-          w[u][0] = n0; w[u][1] = n1; w[u][2] = n2; w[u][3] = n3;
-        }
-        }
-      }
-      /* final round: S[x] = (Te0[x]>>8)&0xff; assemble each output word
-       * from four replicated-table gathers (still conflict-free) */
-#define SB24(idx) ((TE0R(idx) & 0xff00u) << 16)
-#define SB16(idx) ((TE0R(idx) & 0xff00u) << 8)
-#define SB08(idx) (TE0R(idx) & 0xff00u)
-#define SB00(idx) ((TE0R(idx) >> 8) & 0xffu)
-#pragma unroll
-      for (int u = 0; u < L; u++) {
-        if (u >= live) break;
-        uint32_t f0 = (SB24(w[u][0] >> 24) | SB16((w[u][1] >> 16) & 0xff) |
-                       SB08((w[u][2] >> 8) & 0xff) | SB00(w[u][3] & 0xff)) ^
-                      rk[40];
-        uint32_t f1 = (SB24(w[u][1] >> 24) | SB16((w[u][2] >> 16) & 0xff) |
-                       SB08((w[u][3] >> 8) & 0xff) | SB00(w[u][0] & 0xff)) ^
-                      rk[41];
-        uint32_t f2 = (SB24(w[u][2] >> 24) | SB16((w[u][3] >> 16) & 0xff) |
-                       SB08((w[u][0] >> 8) & 0xff) | SB00(w[u][1] & 0xff)) ^
-                      rk[42];
-        uint32_t f3 = (SB24(w[u][3] >> 24) | SB16((w[u][0] >> 16) & 0xff) |
-                       SB08((w[u][1] >> 8) & 0xff) | SB00(w[u][2] & 0xff)) ^
-                      rk[43];
-        unsigned long long v0 =
-            __builtin_bswap64(((unsigned long long)f0 << 32) | f1);
-        unsigned long long v1 =
-            __builtin_bswap64(((unsigned long long)f2 << 32) | f3);
-        if (v0 < a.difficulty) {
-          unsigned int s = atomicAdd(a.hit_count, 1u);
-          if (s < a.hit_cap) {
-            a.hits[s].index = a.index_base + ts[u];
-            a.hits[s].nonce = c * POSTE_NONCES_PER_AES;
-          }
-        }
-        if (v1 < a.difficulty) {
-          unsigned int s = atomicAdd(a.hit_count, 1u);
-          if (s < a.hit_cap) {
-            a.hits[s].index = a.index_base + ts[u];
-            a.hits[s].nonce = c * POSTE_NONCES_PER_AES + 1;
-          }
-        }
-      }
-    }
+ * round's S-box is byte 1 of Te0 — no separate sbox table at all.
+ * Round keys go into registers up front: a.rk accesses inside the round
+ * loop compile to per-round VECTOR global loads (wave-uniform but the
+ * compiler cannot prove it) whose vmcnt waits serialize the cipher loop. */
+struct TeBankrep {
+  static constexpr uint32_t LDS_BYTES = 8192 * 4; /* 32 copies x 1 KiB */
+  static constexpr bool RK_IN_REGS = true;
+  const uint32_t *sTe;
+  uint32_t lane31;
+  __device__ __forceinline__ TeBankrep(uint32_t *lds, const uint32_t *te,
+                                       const uint8_t *) {
+    for (uint32_t i = threadIdx.x; i < 8192; i += blockDim.x)
+      lds[i] = te[i >> 5]; /* consecutive lanes -> consecutive banks */
+    __syncthreads();
+    sTe = lds;
+    lane31 = threadIdx.x & 31;
   }
-#undef TE0R
-#undef SB24
-#undef SB16
-#undef SB08
-#undef SB00
-}
+  template <int T>
+  __device__ __forceinline__ uint32_t te(uint32_t x) const {
+    return sTe[(x << 5) | lane31];
+  }
+  template <int T>
+  static __device__ __forceinline__ uint32_t rot(uint32_t g) {
+    return T == 0 ? g : __builtin_amdgcn_alignbit(g, g, 8 * T);
+  }
+  template <int S>
+  __device__ __forceinline__ uint32_t sb(uint32_t x) const {
+    return te0_sbox<S>(te<0>(x));
+  }
+};
 
-/* 4-table interleaved bank-replicated scan: all four Te tables, each
+/* 4-table interleaved bank-replicated: all four Te tables, each
  * bank-replicated, interleaved so entry (x, t, lane) sits at word
  * x*128 + t*32 + lane%32 — per-gather addressing is one v_lshl_add with
  * the t*128-byte offset folded into the ds_read immediate, and the
  * alignbit rotations of the 1-table variant disappear (~20% of its
  * VALU).  Costs 128 KiB LDS, so one 1024-thread workgroup per CU
  * (16 waves) instead of 20. */
-__global__ void __launch_bounds__(1024)
-post_scan_tt4_kernel(ScanKernelArgs a) {
-  extern __shared__ uint32_t sTe[]; /* 32768 words = 4 tables x 32 copies */
-  for (uint32_t i = threadIdx.x; i < 32768; i += blockDim.x)
-    sTe[i] = a.te[((i >> 5) & 3) * 256 + (i >> 7)];
-  __syncthreads();
-  const uint32_t *t0p = sTe + (threadIdx.x & 31);
-#define TT4(t, idx) t0p[(((uint32_t)(idx)) << 7) + 32 * (t)]
+struct TeTt4 {
+  static constexpr uint32_t LDS_BYTES = 32768 * 4; /* 4 tables x 32 copies */
+  static constexpr bool RK_IN_REGS = true;
+  const uint32_t *t0p;
+  __device__ __forceinline__ TeTt4(uint32_t *lds, const uint32_t *te,
+                                   const uint8_t *) {
+    for (uint32_t i = threadIdx.x; i < 32768; i += blockDim.x)
+      lds[i] = te[((i >> 5) & 3) * 256 + (i >> 7)];
+    __syncthreads();
+    t0p = lds + (threadIdx.x & 31);
+  }
+  template <int T>
+  __device__ __forceinline__ uint32_t te(uint32_t x) const {
+    return t0p[(x << 7) + 32 * T];
+  }
+  template <int T>
+  static __device__ __forceinline__ uint32_t rot(uint32_t g) { return g; }
+  template <int S>
+  __device__ __forceinline__ uint32_t sb(uint32_t x) const {
+    return te0_sbox<S>(te<0>(x));
+  }
+};
 
+/* AES-128 encryption of L blocks p (big-endian words) under the 44 round-key
+ * words rk, in two steps so that a caller can leave out the last round of a
+ * block it will not look at.  aes128_rounds: the whitening and rounds 1-9,
+ * state into w.  BATCHG issues all of a round's gathers before any combine:
+ * it widens the read->use distance so partial lgkmcnt waits overlap the
+ * whole gather batch with the previous combines. */
+template <class Tab, int L, bool BATCHG>
+static __device__ __forceinline__ void
+aes128_rounds(const Tab &tab, const uint32_t (&p)[L][4], const uint32_t *rk,
+              uint32_t (&w)[L][4]) {
+#pragma unroll
+  for (int u = 0; u < L; u++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) w[u][k] = p[u][k] ^ rk[k];
+#pragma unroll
+  for (int r = 1; r < 10; r++) {
+    if (BATCHG) {
+      uint32_t g[L][16];
+#pragma unroll
+      for (int u = 0; u < L; u++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          g[u][4 * q + 0] = tab.template te<0>(w[u][q] >> 24);
+          g[u][4 * q + 1] =
+              tab.template te<1>((w[u][(q + 1) & 3] >> 16) & 0xff);
+          g[u][4 * q + 2] =
+              tab.template te<2>((w[u][(q + 2) & 3] >> 8) & 0xff);
+          g[u][4 * q + 3] = tab.template te<3>(w[u][(q + 3) & 3] & 0xff);
+        }
+#pragma unroll
+      for (int u = 0; u < L; u++)
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+          w[u][q] = Tab::template rot<0>(g[u][4 * q]) ^
+                    Tab::template rot<1>(g[u][4 * q + 1]) ^
+                    Tab::template rot<2>(g[u][4 * q + 2]) ^
+                    Tab::template rot<3>(g[u][4 * q + 3]) ^ rk[4 * r + q];
+    } else {
+#pragma unroll
+      for (int u = 0; u < L; u++) {
+        uint32_t n[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+          n[q] = Tab::template rot<0>(tab.template te<0>(w[u][q] >> 24)) ^
+                 Tab::template rot<1>(tab.template te<1>(
+                     (w[u][(q + 1) & 3] >> 16) & 0xff)) ^
+                 Tab::template rot<2>(tab.template te<2>(
+                     (w[u][(q + 2) & 3] >> 8) & 0xff)) ^
+                 Tab::template rot<3>(
+                     tab.template te<3>(w[u][(q + 3) & 3] & 0xff)) ^
+                 rk[4 * r + q];
+#pragma unroll
+        for (int q = 0; q < 4; q++) w[u][q] = n[q];
+      }
+    }
+  }
+}
+
+/* round 10 of one block: the S-box, no MixColumns; the ciphertext into f */
+template <class Tab>
+static __device__ __forceinline__ void
+aes128_last_round(const Tab &tab, const uint32_t (&w)[4], const uint32_t *rk,
+                  uint32_t (&f)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+    f[q] = (tab.template sb<24>(w[q] >> 24) |
+            tab.template sb<16>((w[(q + 1) & 3] >> 16) & 0xff) |
+            tab.template sb<8>((w[(q + 2) & 3] >> 8) & 0xff) |
+            tab.template sb<0>(w[(q + 3) & 3] & 0xff)) ^
+           rk[40 + q];
+}
+
+/* the two nonce values of a ciphertext, as the difficulty compares them */
+static __device__ __forceinline__ unsigned long long
+aes_nonce_value(const uint32_t (&f)[4], int half) {
+  return __builtin_bswap64(((unsigned long long)f[2 * half] << 32) |
+                           f[2 * half + 1]);
+}
+
+static __device__ __forceinline__ void
+scan_append(const ScanKernelArgs &a, unsigned long long index,
+            uint32_t nonce) {
+  unsigned int s = atomicAdd(a.hit_count, 1u);
+  if (s < a.hit_cap) {
+    a.hits[s].index = index;
+    a.hits[s].nonce = nonce;
+  }
+}
+
+/* Grid-stride scan, L labels per lane and iteration: chain u of the lane at
+ * t0 takes label t0 + u*stride.  A chain past the end is clamped to t0 and
+ * does duplicate work; hits are recorded for the `live` chains only. */
+template <class Tab, int L, bool BATCHG>
+static __device__ __forceinline__ void scan_body(const ScanKernelArgs &a) {
+  extern __shared__ uint32_t scan_lds[];
+  const Tab tab(scan_lds, a.te, a.sbox);
   const unsigned long long stride =
       (unsigned long long)gridDim.x * blockDim.x;
-  /* ILP 4 measured best for this variant (r2d sweep); at one workgroup
-   * per CU there are only 16 waves to hide latency, so deeper chains pay */
-  constexpr int L = POSTE_SCAN_ILP > 4 ? POSTE_SCAN_ILP : 4;
   const unsigned long long span = stride * L;
   for (unsigned long long t0 =
            (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1062,87 +970,43 @@ post_scan_tt4_kernel(ScanKernelArgs a) {
                          ? (int)((a.count - t0 + stride - 1) / stride)
                          : L;
     for (uint32_t c = 0; c < a.n_ciphers; c++) {
-      uint32_t rk[44];
+      const uint32_t *rk = a.rk + c * 44;
+      uint32_t rk_regs[Tab::RK_IN_REGS ? 44 : 1];
+      if constexpr (Tab::RK_IN_REGS) {
 #pragma unroll
-      for (int k = 0; k < 44; k++) rk[k] = a.rk[c * 44 + k];
-      uint32_t w[L][4];
-#pragma unroll
-      for (int u = 0; u < L; u++)
-#pragma unroll
-        for (int k = 0; k < 4; k++) w[u][k] = p[u][k] ^ rk[k];
-#pragma unroll
-      for (int r = 1; r < 10; r++) {
-#pragma unroll
-        for (int u = 0; u < L; u++) {
-          uint32_t n0 = TT4(0, w[u][0] >> 24) ^
-                        TT4(1, (w[u][1] >> 16) & 0xff) ^
-                        TT4(2, (w[u][2] >> 8) & 0xff) ^
-                        TT4(3, w[u][3] & 0xff) ^ rk[4 * r];
-          uint32_t n1 = TT4(0, w[u][1] >> 24) ^
-                        TT4(1, (w[u][2] >> 16) & 0xff) ^
-                        TT4(2, (w[u][3] >> 8) & 0xff) ^
-                        TT4(3, w[u][0] & 0xff) ^ rk[4 * r + 1];
-          uint32_t n2 = TT4(0, w[u][2] >> 24) ^
-                        TT4(1, (w[u][3] >> 16) & 0xff) ^
-                        TT4(2, (w[u][0] >> 8) & 0xff) ^
-                        TT4(3, w[u][1] & 0xff) ^ rk[4 * r + 2];
-          uint32_t n3 = TT4(0, w[u][3] >> 24) ^
-                        TT4(1, (w[u][0] >> 16) & 0xff) ^
-                        TT4(2, (w[u][1] >> 8) & 0xff) ^
-                        TT4(3, w[u][2] & 0xff) ^ rk[4 * r + 3];
-          w[u][0] = n0; w[u][1] = n1; w[u][2] = n2; w[u][3] = n3;
-        }
+        for (int k = 0; k < 44; k++) rk_regs[k] = rk[k];
+        rk = rk_regs;
       }
-      /* final round: S[x] = (Te0[x]>>8)&0xff, t=0 plane */
-#define SB24_4(idx) ((TT4(0, idx) & 0xff00u) << 16)
-#define SB16_4(idx) ((TT4(0, idx) & 0xff00u) << 8)
-#define SB08_4(idx) (TT4(0, idx) & 0xff00u)
-#define SB00_4(idx) ((TT4(0, idx) >> 8) & 0xffu)
+      uint32_t w[L][4];
+      aes128_rounds<Tab, L, BATCHG>(tab, p, rk, w);
 #pragma unroll
       for (int u = 0; u < L; u++) {
         if (u >= live) break;
-        uint32_t f0 = (SB24_4(w[u][0] >> 24) |
-                       SB16_4((w[u][1] >> 16) & 0xff) |
-                       SB08_4((w[u][2] >> 8) & 0xff) |
-                       SB00_4(w[u][3] & 0xff)) ^ rk[40];
-        uint32_t f1 = (SB24_4(w[u][1] >> 24) |
-                       SB16_4((w[u][2] >> 16) & 0xff) |
-                       SB08_4((w[u][3] >> 8) & 0xff) |
-                       SB00_4(w[u][0] & 0xff)) ^ rk[41];
-        uint32_t f2 = (SB24_4(w[u][2] >> 24) |
-                       SB16_4((w[u][3] >> 16) & 0xff) |
-                       SB08_4((w[u][0] >> 8) & 0xff) |
-                       SB00_4(w[u][1] & 0xff)) ^ rk[42];
-        uint32_t f3 = (SB24_4(w[u][3] >> 24) |
-                       SB16_4((w[u][0] >> 16) & 0xff) |
-                       SB08_4((w[u][1] >> 8) & 0xff) |
-                       SB00_4(w[u][2] & 0xff)) ^ rk[43];
-        unsigned long long v0 =
-            __builtin_bswap64(((unsigned long long)f0 << 32) | f1);
-        unsigned long long v1 =
-            __builtin_bswap64(((unsigned long long)f2 << 32) | f3);
-        if (v0 < a.difficulty) {
-          unsigned int s = atomicAdd(a.hit_count, 1u);
-          if (s < a.hit_cap) {
-            a.hits[s].index = a.index_base + ts[u];
-            a.hits[s].nonce = c * POSTE_NONCES_PER_AES;
-          }
-        }
-        if (v1 < a.difficulty) {
-          unsigned int s = atomicAdd(a.hit_count, 1u);
-          if (s < a.hit_cap) {
-            a.hits[s].index = a.index_base + ts[u];
-            a.hits[s].nonce = c * POSTE_NONCES_PER_AES + 1;
-          }
-        }
+        uint32_t f[4];
+        aes128_last_round(tab, w[u], rk, f);
+#pragma unroll
+        for (int h = 0; h < POSTE_NONCES_PER_AES; h++)
+          if (aes_nonce_value(f, h) < a.difficulty)
+            scan_append(a, a.index_base + ts[u], c * POSTE_NONCES_PER_AES + h);
       }
     }
   }
-#undef TT4
-#undef SB24_4
-#undef SB16_4
-#undef SB08_4
-#undef SB00_4
+}
+
+__global__ void __launch_bounds__(POSTE_THREADS)
+post_scan_kernel(ScanKernelArgs a) {
+  scan_body<TeShared, POSTE_SCAN_ILP, false>(a);
+}
+
+template <int THREADS_, bool BATCHG>
+__global__ void __launch_bounds__(THREADS_)
+post_scan_bankrep_kernel(ScanKernelArgs a) {
+  scan_body<TeBankrep, POSTE_SCAN_ILP, BATCHG>(a);
+}
+
+__global__ void __launch_bounds__(1024)
+post_scan_tt4_kernel(ScanKernelArgs a) {
+  scan_body<TeTt4, (POSTE_SCAN_ILP > 4 ? POSTE_SCAN_ILP : 4), false>(a);
 }
 
 /* verification's final predicate: AES-encrypt each recomputed label with
@@ -1151,13 +1015,8 @@ post_scan_tt4_kernel(ScanKernelArgs a) {
  * post_verifier.go:159 -> per-index AES threshold check). */
 __global__ void __launch_bounds__(POSTE_THREADS)
 post_verify_pred_kernel(VerifyPredArgs a) {
-  extern __shared__ uint32_t lds[];
-  uint32_t *sTe = lds;
-  uint8_t *sSbox = (uint8_t *)(sTe + 1024);
-  for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) sTe[i] = a.te[i];
-  for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x)
-    sSbox[i] = a.sbox[i];
-  __syncthreads();
+  extern __shared__ uint32_t verify_lds[];
+  const TeShared tab(verify_lds, a.te, a.sbox);
   const unsigned long long stride =
       (unsigned long long)gridDim.x * blockDim.x;
   for (unsigned long long t =
@@ -1166,46 +1025,14 @@ post_verify_pred_kernel(VerifyPredArgs a) {
     const uint32_t pidx = a.task_proof[t];
     const uint32_t *rk = a.rk + (unsigned long long)pidx * 44;
     uint4 lraw = a.labels2[2 * t]; /* first 16 B of the full label */
-    uint32_t w0 = __builtin_bswap32(lraw.x) ^ rk[0];
-    uint32_t w1 = __builtin_bswap32(lraw.y) ^ rk[1];
-    uint32_t w2 = __builtin_bswap32(lraw.z) ^ rk[2];
-    uint32_t w3 = __builtin_bswap32(lraw.w) ^ rk[3];
-#pragma unroll
-    for (int r = 1; r < 10; r++) {
-      uint32_t n0 = sTe[w0 >> 24] ^ sTe[256 + ((w1 >> 16) & 0xff)] ^
-                    sTe[512 + ((w2 >> 8) & 0xff)] ^ sTe[768 + (w3 & 0xff)] ^
-                    rk[4 * r];
-      uint32_t n1 = sTe[w1 >> 24] ^ sTe[256 + ((w2 >> 16) & 0xff)] ^
-                    sTe[512 + ((w3 >> 8) & 0xff)] ^ sTe[768 + (w0 & 0xff)] ^
-                    rk[4 * r + 1];
-      uint32_t n2 = sTe[w2 >> 24] ^ sTe[256 + ((w3 >> 16) & 0xff)] ^
-                    sTe[512 + ((w0 >> 8) & 0xff)] ^ sTe[768 + (w1 & 0xff)] ^
-                    rk[4 * r + 2];
-      uint32_t n3 = sTe[w3 >> 24] ^ sTe[256 + ((w0 >> 16) & 0xff)] ^
-                    sTe[512 + ((w1 >> 8) & 0xff)] ^ sTe[768 + (w2 & 0xff)] ^
-                    rk[4 * r + 3];
-      w0 = n0; w1 = n1; w2 = n2; w3 = n3;
-    }
-    uint32_t f0 = (((uint32_t)sSbox[w0 >> 24] << 24) |
-                   ((uint32_t)sSbox[(w1 >> 16) & 0xff] << 16) |
-                   ((uint32_t)sSbox[(w2 >> 8) & 0xff] << 8) |
-                   sSbox[w3 & 0xff]) ^ rk[40];
-    uint32_t f1 = (((uint32_t)sSbox[w1 >> 24] << 24) |
-                   ((uint32_t)sSbox[(w2 >> 16) & 0xff] << 16) |
-                   ((uint32_t)sSbox[(w3 >> 8) & 0xff] << 8) |
-                   sSbox[w0 & 0xff]) ^ rk[41];
-    uint32_t f2 = (((uint32_t)sSbox[w2 >> 24] << 24) |
-                   ((uint32_t)sSbox[(w3 >> 16) & 0xff] << 16) |
-                   ((uint32_t)sSbox[(w0 >> 8) & 0xff] << 8) |
-                   sSbox[w1 & 0xff]) ^ rk[42];
-    uint32_t f3 = (((uint32_t)sSbox[w3 >> 24] << 24) |
-                   ((uint32_t)sSbox[(w0 >> 16) & 0xff] << 16) |
-                   ((uint32_t)sSbox[(w1 >> 8) & 0xff] << 8) |
-                   sSbox[w2 & 0xff]) ^ rk[43];
-    unsigned long long v =
-        a.half[pidx] == 0
-            ? __builtin_bswap64(((unsigned long long)f0 << 32) | f1)
-            : __builtin_bswap64(((unsigned long long)f2 << 32) | f3);
+    const uint32_t p[1][4] = {
+        {__builtin_bswap32(lraw.x), __builtin_bswap32(lraw.y),
+         __builtin_bswap32(lraw.z), __builtin_bswap32(lraw.w)}};
+    uint32_t w[1][4], f[4];
+    aes128_rounds<TeShared, 1, false>(tab, p, rk, w);
+    aes128_last_round(tab, w[0], rk, f);
+    unsigned long long v = a.half[pidx] == 0 ? aes_nonce_value(f, 0)
+                                             : aes_nonce_value(f, 1);
     a.pass[t] = v < a.difficulty[pidx] ? 1 : 0;
   }
 }
@@ -1558,9 +1385,8 @@ hipError_t poste_launch_label_audit(const AuditKernelArgs *args,
 hipError_t poste_launch_verify_pred_kernel(const VerifyPredArgs *args,
                                            uint32_t blocks,
                                            hipStream_t stream) {
-  size_t lds = 1024 * 4 + 256;
   hipLaunchKernelGGL(post_verify_pred_kernel, dim3(blocks),
-                     dim3(POSTE_THREADS), lds, stream, *args);
+                     dim3(POSTE_THREADS), TeShared::LDS_BYTES, stream, *args);
   return hipGetLastError();
 }
 
@@ -1598,117 +1424,99 @@ uint64_t poste_label_resident_slots(uint32_t gap_shift) {
   return (uint64_t)blocks_per_cu * cus * (POSTE_THREADS / 4);
 }
 
-/* POST_SCAN_MAX_BLOCKS lowers a scan variant's block cap (never raises it,
- * never below 1; unset, zero or unparsable = the variant's own cap).  With
- * a cap of a few blocks a few thousand labels already make every ILP chain
- * live and the grid-stride loop iterate — what mainnet's 2^24-label chunks
- * do at the full grid — so tests reach those paths at small sizes. */
-static uint32_t scan_block_cap(uint32_t variant_cap) {
-  const char *e = getenv("POST_SCAN_MAX_BLOCKS");
-  if (!e) return variant_cap;
-  long v = strtol(e, nullptr, 10);
-  return v >= 1 && v < (long)variant_cap ? (uint32_t)v : variant_cap;
+/* The scan variants, indexed by ScanVariant: name, threads per block, LDS
+ * bytes, block cap.  The caps keep the grid at 2^21 lanes. */
+static const struct {
+  const char *name;
+  ScanPlan plan;
+} SCAN_VARIANTS[] = {
+    {"shared",
+     {POSTE_SCAN_SHARED, POSTE_THREADS, TeShared::LDS_BYTES, 8192}},
+    {"bankrep",
+     {POSTE_SCAN_BANKREP, POSTE_THREADS, TeBankrep::LDS_BYTES, 8192}},
+    {"bankrepbg",
+     {POSTE_SCAN_BANKREP_BG, POSTE_THREADS, TeBankrep::LDS_BYTES, 8192}},
+    {"bankrep512", {POSTE_SCAN_BANKREP512, 512, TeBankrep::LDS_BYTES, 4096}},
+    {"bankrep512bg",
+     {POSTE_SCAN_BANKREP512_BG, 512, TeBankrep::LDS_BYTES, 4096}},
+    {"tt4", {POSTE_SCAN_TT4, 1024, TeTt4::LDS_BYTES, 2048}},
+};
+constexpr int SCAN_VARIANT_COUNT =
+    (int)(sizeof SCAN_VARIANTS / sizeof SCAN_VARIANTS[0]);
+static_assert(SCAN_VARIANT_COUNT == POSTE_SCAN_TT4 + 1,
+              "one SCAN_VARIANTS row per ScanVariant, in enum order");
+
+const char *poste_scan_variant_name(int variant) {
+  return variant >= 0 && variant < SCAN_VARIANT_COUNT
+             ? SCAN_VARIANTS[variant].name
+             : "?";
 }
 
-hipError_t poste_launch_scan_kernel(const ScanKernelArgs *args,
-                                    uint32_t blocks, hipStream_t stream) {
-  /* POST_SCAN_MODE: shared = round-1 shared-T-table kernel; tt4 =
-   * 4-table/128KiB replicated kernel; bankrep512 / bankrepbg /
-   * bankrep512bg = bank-replicated at 512-thread workgroups and/or
-   * batched-gather scheduling; default = bank-replicated Te0 at 256.
-   * Read per launch (launches are ms-scale) so tests can A/B kernels
-   * within one process. */
-  const uint32_t cap = scan_block_cap(8192);
-  if (blocks > cap) blocks = cap;
-  const char *e = getenv("POST_SCAN_MODE");
-  const char *m = e ? e : "tt4"; /* fastest measured (r2d sweep); falls
-                                    back to bankrep without 128 KiB LDS */
-  if (strcmp(m, "shared") == 0) {
-    size_t lds = 1024 * 4 + 256;
-    hipLaunchKernelGGL(post_scan_kernel, dim3(blocks), dim3(POSTE_THREADS),
-                       lds, stream, *args);
-    return hipGetLastError();
-  }
-  if (strcmp(m, "tt4") == 0) {
-    static bool attr_ok = [] {
-      return hipFuncSetAttribute(
-                 (const void *)post_scan_tt4_kernel,
-                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                 32768 * 4) == hipSuccess;
-    }();
-    if (attr_ok) {
-      uint32_t b4 = (uint32_t)((args->count + 1023) / 1024);
-      const uint32_t cap4 = scan_block_cap(2048);
-      if (b4 > cap4) b4 = cap4;
-      if (b4 == 0) b4 = 1;
-      hipLaunchKernelGGL(post_scan_tt4_kernel, dim3(b4), dim3(1024),
-                         32768 * 4, stream, *args);
-      return hipGetLastError();
+hipError_t poste_scan_plan(const char *mode, const char *max_blocks,
+                           int allow_fallback, ScanPlan *out) {
+  /* tt4 is the fastest measured (r2d sweep) */
+  int v = mode ? POSTE_SCAN_BANKREP : POSTE_SCAN_TT4;
+  for (const auto &e : SCAN_VARIANTS)
+    if (mode && strcmp(mode, e.name) == 0) v = e.plan.variant;
+  if (v == POSTE_SCAN_TT4) {
+    const hipError_t e = hipFuncSetAttribute(
+        (const void *)post_scan_tt4_kernel,
+        hipFuncAttributeMaxDynamicSharedMemorySize, TeTt4::LDS_BYTES);
+    if (e != hipSuccess && !allow_fallback) return e;
+    if (e != hipSuccess) {
+      v = POSTE_SCAN_BANKREP;
+      (void)hipGetLastError(); /* the refusal must not meet the launch's */
     }
-    m = "bankrep"; /* 128 KiB dynamic LDS unavailable */
   }
-  const bool bg = strstr(m, "bg") != nullptr;
-  const bool wide = strstr(m, "512") != nullptr;
-  size_t lds = 8192 * 4; /* 32 bank-strided copies of Te0 */
-  if (wide) {
-    uint32_t b5 = (uint32_t)((args->count + 511) / 512);
-    const uint32_t cap5 = scan_block_cap(4096);
-    if (b5 > cap5) b5 = cap5;
-    if (b5 == 0) b5 = 1;
-    if (bg)
-      hipLaunchKernelGGL((post_scan_bankrep_kernel<512, true>), dim3(b5),
-                         dim3(512), lds, stream, *args);
-    else
-      hipLaunchKernelGGL((post_scan_bankrep_kernel<512, false>), dim3(b5),
-                         dim3(512), lds, stream, *args);
-  } else if (bg) {
-    hipLaunchKernelGGL((post_scan_bankrep_kernel<POSTE_THREADS, true>),
-                       dim3(blocks), dim3(POSTE_THREADS), lds, stream,
-                       *args);
-  } else {
-    hipLaunchKernelGGL((post_scan_bankrep_kernel<POSTE_THREADS, false>),
-                       dim3(blocks), dim3(POSTE_THREADS), lds, stream,
-                       *args);
+  *out = SCAN_VARIANTS[v].plan;
+  /* POST_SCAN_MAX_BLOCKS: lowers the cap, never raises it, never below 1;
+   * zero or unparsable = the variant's own.  With a cap of a few blocks a
+   * few thousand labels already make every ILP chain live and the
+   * grid-stride loop iterate — what mainnet's 2^24-label chunks do at the
+   * full grid — so tests reach those paths at small sizes. */
+  if (max_blocks) {
+    const long m = strtol(max_blocks, nullptr, 10);
+    if (m >= 1 && m < (long)out->max_blocks) out->max_blocks = (uint32_t)m;
   }
-  return hipGetLastError();
+  return hipSuccess;
 }
 
-/* The proving scan over a batch that already lies in device memory (an init
- * batch behind its tail kernels), on the caller's stream.  The
- * kernels are those of poste_launch_scan_kernel, unchanged; what differs is
- * that nothing is read from the environment per launch: the session picks
- * the variant once, prepares it once (the 128 KiB dynamic-LDS opt-in of tt4
- * is a function attribute, set outside any stream), and fixes the grid cap. */
-hipError_t poste_scan_resident_prepare(int variant) {
-  if (variant == POSTE_SCAN_RESIDENT_BANKREP) return hipSuccess;
-  if (variant != POSTE_SCAN_RESIDENT_TT4) return hipErrorInvalidValue;
-  return hipFuncSetAttribute((const void *)post_scan_tt4_kernel,
-                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                             32768 * 4);
-}
-
-uint32_t poste_scan_resident_threads(int variant) {
-  return variant == POSTE_SCAN_RESIDENT_TT4 ? 1024 : POSTE_THREADS;
-}
-
-hipError_t poste_launch_scan_resident(const ScanKernelArgs *args, int variant,
-                                      uint32_t max_blocks,
-                                      hipStream_t stream) {
+hipError_t poste_launch_scan(const ScanKernelArgs *args, const ScanPlan *plan,
+                             hipStream_t stream) {
   if (!args->labels || !args->hits || !args->hit_count || args->count == 0 ||
-      max_blocks == 0)
+      plan->max_blocks == 0)
     return hipErrorInvalidValue;
-  const uint32_t threads = poste_scan_resident_threads(variant);
-  const uint64_t need = (args->count + threads - 1) / threads;
-  const uint32_t blocks = need < max_blocks ? (uint32_t)need : max_blocks;
-  if (variant == POSTE_SCAN_RESIDENT_TT4)
-    hipLaunchKernelGGL(post_scan_tt4_kernel, dim3(blocks), dim3(1024),
-                       32768 * 4, stream, *args);
-  else if (variant == POSTE_SCAN_RESIDENT_BANKREP)
-    hipLaunchKernelGGL((post_scan_bankrep_kernel<POSTE_THREADS, false>),
-                       dim3(blocks), dim3(POSTE_THREADS), 8192 * 4, stream,
-                       *args);
-  else
+  const uint64_t need = (args->count + plan->threads - 1) / plan->threads;
+  const dim3 grid(need < plan->max_blocks ? (uint32_t)need : plan->max_blocks);
+  const dim3 block(plan->threads);
+  const size_t lds = plan->lds_bytes;
+  switch (plan->variant) {
+  case POSTE_SCAN_SHARED:
+    hipLaunchKernelGGL(post_scan_kernel, grid, block, lds, stream, *args);
+    break;
+  case POSTE_SCAN_BANKREP:
+    hipLaunchKernelGGL((post_scan_bankrep_kernel<POSTE_THREADS, false>), grid,
+                       block, lds, stream, *args);
+    break;
+  case POSTE_SCAN_BANKREP_BG:
+    hipLaunchKernelGGL((post_scan_bankrep_kernel<POSTE_THREADS, true>), grid,
+                       block, lds, stream, *args);
+    break;
+  case POSTE_SCAN_BANKREP512:
+    hipLaunchKernelGGL((post_scan_bankrep_kernel<512, false>), grid, block,
+                       lds, stream, *args);
+    break;
+  case POSTE_SCAN_BANKREP512_BG:
+    hipLaunchKernelGGL((post_scan_bankrep_kernel<512, true>), grid, block,
+                       lds, stream, *args);
+    break;
+  case POSTE_SCAN_TT4:
+    hipLaunchKernelGGL(post_scan_tt4_kernel, grid, block, lds, stream, *args);
+    break;
+  default:
     return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
+
 }

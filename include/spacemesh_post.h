@@ -547,8 +547,10 @@ int post_seal_digest_stream(const uint8_t *labels, uint64_t count,
  * Environment, read once by post_init_enable_proof and never per launch:
  * POST_INIT_PROOF_SCAN = bankrep (default) or tt4 picks the scan kernel, both
  * leave identical parts (anything else: POST_ERR_INVALID_ARGS, judged before
- * the dir is touched); POST_SCAN_MAX_BLOCKS lowers the scan's grid cap as it
- * does for post_prove; POST_INIT_PROOF_DEBUG times the scan of every batch
+ * the dir is touched; a tt4 whose 128 KiB of LDS the device refuses is an
+ * error too, there is no fallback here); POST_SCAN_MAX_BLOCKS lowers the
+ * scan's grid cap as it does for post_prove; the session keeps the resulting
+ * scan plan; POST_INIT_PROOF_DEBUG times the scan of every batch
  * with device events and prints the figures on stderr when the range is
  * complete.
  *

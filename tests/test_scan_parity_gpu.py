@@ -321,3 +321,14 @@ def test_hit_cap_overflow_leaves_no_state(mode):
         assert "overflow" in str(ei.value)
         got = gpu_hits(labels, count, k1, cap=len(want) + 1024)
     assert sorted(got) == want
+
+
+# ----------------------------- f. unknown mode -----------------------------
+
+def test_unknown_mode_runs_the_fallback():
+    """A POST_SCAN_MODE that is none of the six names runs the default
+    fallback (bankrep)."""
+    labels, k1, want = chain_case(3001)
+    with scan_env("fastest", max_blocks=2):
+        got = gpu_hits(labels, 3001, k1, cap=len(want) + 1024)
+    assert sorted(got) == want
